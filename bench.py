@@ -10,13 +10,21 @@ descriptors, search them (top-100 cosine kNN, exact ordering) against a
 -> on-GPU merge).  Per-rank work is fixed as ranks grow (images per rank,
 and queries x local rows per rank), so scaling is weak.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
-Rank 0 prints ONE JSON line.  Also measured (separate loops, same process):
-extract-only images/s and kNN-only queries/s at Q=1024 against the 1M DB.
-The CPU baseline (rank 0, N=1 only) times the oracle restatement of the
-reference path on a bounded sample (oracle/ is the checker, not the product).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K
+steps and prints the headline (value, ms_per_step, the extractor roofline of
+those steps).  --dump-outputs DIR writes what the last timed step returned
+(descriptors.npy, knn_scores.npy, knn_indices.npy); the inputs are seeded, so
+two builds can be compared output for output.  --full also measures (separate
+loops, same process): the other 16-bit precision end to end, extract-only
+images/s, PCIe-inclusive extraction, kNN-only queries/s at Q=1024 against the
+1M DB, the collectives (N > 1), the local head, single-image latency, the
+drop-in file path, every precision with its reference parity, configs 3/4/5,
+and the CPU baseline (rank 0, N=1 only), which times the oracle restatement
+of the reference path on a bounded sample (oracle/ is the checker, not the
+product).
 """
 
 import argparse
@@ -112,7 +120,40 @@ def parse():
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU baseline threads (0: OMP_NUM_THREADS, else the usable CPUs), pinned one per physical "
                          "core of one socket")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every sub-benchmark and check (other precisions, extract-only, "
+                         "PCIe, kNN-only, collectives, local head, latency, configs 3/4/5 with reference parity, the "
+                         "CPU baseline); without it only the headline steps run and those fields are null / absent")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy: its "
+                         "descriptors (D x B float32) and the scores / indices of the last search (float64)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:   # a plain run: set up, warm up, time the steps, print the line
+        args.alt_steps = args.pcie_steps = args.knn_q = args.local_kpts = args.latency = 0
+        args.extras, args.no_cpu_baseline = False, True
+    return args
+
+
+DUMP_BYTES_MAX = 64 << 20   # all of --dump-outputs together
+
+
+def dump_outputs(path, arrays):
+    """{name: tensor} -> path/<name>.npy (float32 stays float32, everything else float64).
+    Arrays over their share of DUMP_BYTES_MAX are cut to a fixed, seeded sample of their
+    leading-dimension slices (sorted, so the same slices in every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES_MAX // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        if a.nbytes > share and a.ndim:
+            per = max(1, a.nbytes // a.shape[0])
+            keep = np.sort(np.random.default_rng(0xD0A7).choice(a.shape[0], max(1, share // per), replace=False))
+            a = a[keep]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def conv_flops_per_image(body, h, w):
@@ -724,6 +765,7 @@ def main():
 
     QB = 0 if args.query_batch <= 0 else max(B, args.query_batch // B * B)  # queries per rank per search
     queued = []   # this rank's extracted, not yet searched descriptors (D x B each)
+    last = {}     # what the latest step returned: its descriptors, the latest search's (scores, idx)
 
     def search_queued():
         """launch the certified search of the queued descriptors on the search stream"""
@@ -746,6 +788,7 @@ def main():
         prev, requeried, searches = None, 0, 0
         for i in range(n):
             queued.append(extract_all(record))
+            last["descriptors"] = queued[-1]
             if QB == 0 or len(queued) * B >= QB or i == n - 1:
                 res = search_queued()
                 searches += 1
@@ -754,6 +797,7 @@ def main():
                 prev = res
         if prev is not None:
             requeried += resolve(prev)
+            last["knn_scores"], last["knn_indices"] = prev[0], prev[1]
         return requeried, searches
 
     EB = max(1, min(args.extract_batch, B))
@@ -811,6 +855,8 @@ def main():
             dist.barrier()
         elapsed = max_over_ranks(time.perf_counter() - t0)
         body_ms = sum(a.elapsed_time(b) for a, b in ev_pairs) / args.steps   # extractor time per step
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last)
 
         # the same step in the other 16-bit precision (bf16 = BASELINE config 2 beside
         # the fp16 headline, which meets the north_star descriptor bar)
@@ -847,17 +893,19 @@ def main():
         # extract-only loop (same net, no matching); warm-up first: the model swap and
         # empty_cache above returned the activation buffers, which must not be
         # re-allocated inside the timed loop
-        n_ext = max(3, args.steps // 2)
-        for _ in range(max(2, args.warmup)):
-            extract_all(False)
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        t1 = time.perf_counter()
-        for _ in range(n_ext):
-            extract_all(False)
-        torch.cuda.synchronize()
-        ext_only = n_ext * B / max_over_ranks(time.perf_counter() - t1)
+        ext_only = None
+        if args.full:
+            n_ext = max(3, args.steps // 2)
+            for _ in range(max(2, args.warmup)):
+                extract_all(False)
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
+            t1 = time.perf_counter()
+            for _ in range(n_ext):
+                extract_all(False)
+            torch.cuda.synchronize()
+            ext_only = n_ext * B / max_over_ranks(time.perf_counter() - t1)
 
         # PCIe-inclusive extraction (not `value`: the timed step starts with the
         # images resident in HBM): the step's B images from pinned host memory,
@@ -1002,7 +1050,7 @@ def main():
         # (B x D fp32 per rank) and the per-shard top-k exchange (one all-gather of
         # the packed (score, index) lists + the merge), HIP events on this stream
         comm = None
-        if world > 1:
+        if args.full and world > 1:
             qd = torch.randn((B, args.dim), generator=g, device=dev)
             sl, il = index.local.search(all_gather_stacked(qd).reshape(world * B, args.dim), args.k, verify=False)
             ea, eb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -1110,6 +1158,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": elapsed / args.steps * 1e3,
         "requeried": step_requeried,
         "searches": step_searches,
@@ -1145,7 +1194,7 @@ def main():
                             "peak_hbm_gbs": PEAK_HBM_GBS,
                             "note": "sum over the body's 53 conv layers of max(FLOPs/peak_mfma, algorithmic HBM bytes/"
                                     "peak_hbm) for the step's images, over the measured extractor time"},
-        "extract_images_per_sec": ext_only * world,
+        "extract_images_per_sec": ext_only * world if ext_only is not None else None,
         "build": build_provenance(),
         "dist": {"world_size": dist.get_world_size() if dist.is_initialized() else 1,
                  "backend": dist.get_backend() if dist.is_initialized() else None,

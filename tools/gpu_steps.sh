@@ -28,23 +28,23 @@ for STEP in "$@"; do
       timeout -k 10 300 python -u tools/layer_bench.py --batch 128 --precision fp16 --tune "$TUNE" > "$OUT/layers_$i.txt" 2>&1 || { tail -20 "$OUT/layers_$i.txt"; exit 1; }
       echo "== layers tune=$TUNE"; grep -v amdgpu.ids "$OUT/layers_$i.txt" ;;
     bench)
-      timeout -k 10 600 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+      timeout -k 10 600 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
       tail -c 3000 "$OUT/bench.json" ;;
     benchq:*)
       TUNE=${STEP#benchq:}
-      timeout -k 10 300 python -u bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras --latency 0 --pcie-steps 0 --local-kpts 0 --fp16-steps 0 --tune "$TUNE" > "$OUT/benchq_$i.json" 2> "$OUT/benchq_$i.err" || { tail -20 "$OUT/benchq_$i.err"; exit 1; }
+      timeout -k 10 300 python -u bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extras --latency 0 --pcie-steps 0 --local-kpts 0 --fp16-steps 0 --tune "$TUNE" > "$OUT/benchq_$i.json" 2> "$OUT/benchq_$i.err" || { tail -20 "$OUT/benchq_$i.err"; exit 1; }
       python3 -c "
 import json
 d=json.loads(open('$OUT/benchq_$i.json').read().strip().splitlines()[-1]); print('tune=%-12s' % '$TUNE', '%.1f img/s' % d['value'], '%.3f ms' % d['ms_per_step'], 'knn %.3f ms' % (d.get('knn') or {}).get('ms_per_batch', 0), 'extract %.1f img/s' % d['extract_images_per_sec'], 'body %.3f ms' % d['roofline_layers']['measured_ms'])" ;;
     benchargs:*)
       BARGS=${STEP#benchargs:}
-      timeout -k 10 300 python -u bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras --latency 0 --pcie-steps 0 --local-kpts 0 --fp16-steps 0 $BARGS > "$OUT/benchargs_$i.json" 2> "$OUT/benchargs_$i.err" || { tail -20 "$OUT/benchargs_$i.err"; exit 1; }
+      timeout -k 10 300 python -u bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extras --latency 0 --pcie-steps 0 --local-kpts 0 --fp16-steps 0 $BARGS > "$OUT/benchargs_$i.json" 2> "$OUT/benchargs_$i.err" || { tail -20 "$OUT/benchargs_$i.err"; exit 1; }
       python3 -c "
 import json
 d=json.loads(open('$OUT/benchargs_$i.json').read().strip().splitlines()[-1]); print('args=%-30s' % '$BARGS', '%.1f img/s' % d['value'], '%.3f ms' % d['ms_per_step'], 'knn %.3f ms' % (d.get('knn') or {}).get('ms_per_batch', 0), 'extract %.1f img/s' % d['extract_images_per_sec'], 'body %.3f ms' % d['roofline_layers']['measured_ms'])" ;;
     benchenv:*)
       ENVV=${STEP#benchenv:}
-      env $ENVV timeout -k 10 300 python -u bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras --latency 0 --pcie-steps 0 --local-kpts 0 --fp16-steps 0 > "$OUT/benchenv_$i.json" 2> "$OUT/benchenv_$i.err" || { tail -20 "$OUT/benchenv_$i.err"; exit 1; }
+      env $ENVV timeout -k 10 300 python -u bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extras --latency 0 --pcie-steps 0 --local-kpts 0 --fp16-steps 0 > "$OUT/benchenv_$i.json" 2> "$OUT/benchenv_$i.err" || { tail -20 "$OUT/benchenv_$i.err"; exit 1; }
       python3 -c "
 import json
 d=json.loads(open('$OUT/benchenv_$i.json').read().strip().splitlines()[-1]); print('env=%-24s' % '$ENVV', '%.1f img/s' % d['value'], '%.3f ms' % d['ms_per_step'], 'knn %.3f ms' % (d.get('knn') or {}).get('ms_per_batch', 0), 'extract %.1f img/s' % d['extract_images_per_sec'], 'body %.3f ms' % d['roofline_layers']['measured_ms'])" ;;
@@ -54,7 +54,7 @@ d=json.loads(open('$OUT/benchenv_$i.json').read().strip().splitlines()[-1]); pri
       tail -3 "$OUT/pytest_gpu.log" ;;
     prof)
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run \
-        --output-format csv -- python3 "$ROOT/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-extras --latency 0 --pcie-steps 0 --fp16-steps 0 \
+        --output-format csv -- python3 "$ROOT/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline --no-extras --latency 0 --pcie-steps 0 --fp16-steps 0 \
         > "$OUT/prof_bench.json" 2> "$OUT/prof.err") || { tail -20 "$OUT/prof.err"; exit 1; }
       tail -c 1500 "$OUT/prof_bench.json" ;;
     knnprof:*)

@@ -7,7 +7,7 @@ set -e
 mkdir -p gpurun_out/w4
 for N in 2 4; do
   timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-    --master-port $((29530 + N)) bench.py --gpus $N --steps 10 --warmup 2 --alt-steps 0 --dist-backend gloo --one-device \
+    --master-port $((29530 + N)) bench.py --gpus $N --full --steps 10 --warmup 2 --alt-steps 0 --dist-backend gloo --one-device \
     --no-cpu-baseline --no-extras --latency 0 --pcie-steps 0 --local-kpts 0 \
     > gpurun_out/w4/bench_w$N.json 2> gpurun_out/w4/bench_w$N.err
   python3 -c "
