@@ -33,6 +33,11 @@ class ConvDesc(ctypes.Structure):
                [("slope", ctypes.c_float), ("flags", ctypes.c_int)]
 
 
+class Region(ctypes.Structure):
+    """rr_region: one pooling rectangle of a stage map."""
+    _fields_ = [(n, ctypes.c_uint16) for n in ("y0", "x0", "h", "w")]
+
+
 _vp, _i, _ll, _f, _d, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_double, ctypes.c_size_t
 _SIGS = {
     "rr_version": ([], _i),
@@ -60,6 +65,8 @@ _SIGS = {
     "rr_resize_bilinear": ([_vp, _i, _i, _i, _vp, _i, _i, _d, _d, _vp], _i),
     "rr_global_pool": ([_vp, _i, _i, _i, _i, _i, _f, _f, _vp, _i, _vp], _i),
     "rr_global_pool_pdev": ([_vp, _i, _i, _i, _i, _i, _f, _vp, _f, _vp, _i, _vp], _i),
+    "rr_region_pool": ([_vp, _i, _i, _i, _i, ctypes.POINTER(Region), _i, _i, _f, _vp, _i, _f, _vp, _i, _vp], _i),
+    "rr_region_aggregate": ([_vp, _i, _i, _i, _i, _f, _vp, _vp], _i),
     "rr_l2n_rows": ([_vp, _i, _i, _f, _vp, _vp], _i),
     "rr_linear_rows": ([_vp, _i, _i, _vp, _vp, _i, _vp, _vp], _i),
     "rr_head_workspace_bytes": ([_i, _i], _sz),

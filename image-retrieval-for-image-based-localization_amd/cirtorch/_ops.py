@@ -334,7 +334,7 @@ def global_pool(x, mode, p=3.0, eps=1e-6):
     p_dev = None
     if torch.is_tensor(p):
         if p.numel() != 1:
-            raise NotImplementedError("per-channel GeM exponents (GeMmp) are out of scope")
+            raise ValueError("global_pool takes one exponent; per-channel exponents go through region_pool")
         E.require_gpu(p)
         p_dev = p.detach().reshape(1)
         if p_dev.dtype != torch.float32:
@@ -360,6 +360,56 @@ def global_pool(x, mode, p=3.0, eps=1e-6):
     else:
         E.check(E.lib().rr_global_pool(E.ptr(x), n, c, h * w, layout, mode, float(p), float(eps), E.ptr(out),
                                        E.dtype_code(x.dtype), _st()), "rr_global_pool")
+    return out
+
+
+def region_pool(x, regions, mode, p=3.0, eps=1e-6):
+    """x: [N, C, H, W] (channels_last view: read in place; anything else is
+    converted to NHWC once) -> [N, R, C] float32, one pooled vector per
+    rectangle of ``regions`` ((y0, x0, h, w) tuples, ``roi_regions``), all of
+    them in one pass over the map (rr_region_pool).  p: a float; a one-element
+    GPU tensor (a learnable ``GeM.p``), read by the kernel; or a C-element GPU
+    tensor of per-channel exponents (GeMmp)."""
+    E.require_gpu(x)
+    n, c, h, w = x.shape
+    p_dev, p_count = None, 0
+    if torch.is_tensor(p):
+        if p.numel() not in (1, c):
+            raise ValueError("GeM exponents: one, or one per channel (%d); got %d" % (c, p.numel()))
+        E.require_gpu(p)
+        p_dev = p.detach().reshape(-1)
+        if p_dev.dtype != torch.float32:
+            p_dev = p_dev.float()
+        p_count, p = p_dev.numel(), 1.0
+    if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        x = x.float()
+    xh = x.permute(0, 2, 3, 1)  # NHWC view
+    cp = (c + 3) // 4 * 4
+    if cp != c:
+        # the kernel reads 4 channels per lane: zero channels are pooled and dropped
+        xh = torch.nn.functional.pad(xh, (0, cp - c))
+        if p_count == c:
+            p_dev = torch.nn.functional.pad(p_dev, (0, cp - c), value=1.0)
+        p_count = cp if p_count == c else p_count
+    xh = xh.contiguous()  # no copy for a channels_last tensor
+    p_dev = p_dev.contiguous() if p_dev is not None else None
+    R = len(regions)
+    tab = (E.Region * max(R, 1))(*[E.Region(*[int(v) for v in r]) for r in regions])
+    out = torch.empty((n, R, cp), dtype=torch.float32, device=x.device)
+    E.check(E.lib().rr_region_pool(E.ptr(xh), n, h, w, cp, tab, R, mode, float(p), E.ptr(p_dev), p_count,
+                                   float(eps), E.ptr(out), E.dtype_code(xh.dtype), _st()), "rr_region_pool")
+    return out if cp == c else out[:, :, :c].contiguous()
+
+
+def region_aggregate(rv, l2n_rows=False, eps=1e-6):
+    """rv: [N, R, D] float32 region descriptors -> L2N(sum_r rv) [N, D];
+    l2n_rows: L2-normalise every region row first (rr_region_aggregate)."""
+    E.require_gpu(rv)
+    rv = rv.contiguous().float()
+    n, R, dim = rv.shape
+    out = torch.empty((n, dim), dtype=torch.float32, device=rv.device)
+    E.check(E.lib().rr_region_aggregate(E.ptr(rv), n, R, dim, int(bool(l2n_rows)), float(eps), E.ptr(out), _st()),
+            "rr_region_aggregate")
     return out
 
 

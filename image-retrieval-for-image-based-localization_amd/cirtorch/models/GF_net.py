@@ -26,6 +26,7 @@ from .. import _ops
 from ..algos.GF_algo import globalFeatureAlgo
 from ..backbones import resnet as _resnet
 from ..modules.heads.global_head import globalHead
+from ..modules.pools import POOLING_LAYERS
 from ..utils.parallel import PackedSequence
 
 from ..modules.utils import OUTPUT_DIM  # noqa: E402  (reference cirtorch/modules/utils.py:61-79)
@@ -145,20 +146,28 @@ class ImageRetrievalNet(nn.Module):
 
 
 def make_net(architecture="resnet50", pooling="gem", whitening=True, mean=None, std=None, precision="bf16",
-             p=3.0):
+             p=3.0, regional=False, regional_whitening=True, L=3):
     """Build body + globalHead + algo the way ``scripts/train_globalF.py:make_model`` does
-    (``:240-356``): leaky_relu(0.01) ABN, GeM(p, 1e-6), L2N, Linear(dim, dim) whitening."""
+    (``:240-356``): leaky_relu(0.01) ABN, GeM(p, 1e-6), L2N, Linear(dim, dim) whitening.
+    regional=True (the ``-reg`` networks of ``scripts/test.py:42-43,98,124``) wraps the pool in
+    ``Rpool(pool, Linear(dim, dim), L)`` (``regional_whitening=False``: no regional Linear)."""
     body = _resnet.__dict__[architecture](precision=precision)
     dim = OUTPUT_DIM[architecture]
-    pname = {"gem": "GeM", "mac": "MAC", "spoc": "SPoC"}[pooling.lower()]
-    params = {"p": p, "eps": 1e-6} if pname == "GeM" else {}
+    pname = {"gem": "GeM", "mac": "MAC", "spoc": "SPoC", "gemmp": "GeMmp"}[pooling.lower()]
+    params = {"p": p, "eps": 1e-6} if pname in ("GeM", "GeMmp") else {}
+    if regional:
+        if pname == "GeMmp":
+            params["mp"] = dim
+        rwhiten = nn.Linear(dim, dim, bias=True) if regional_whitening else None
+        params = {"rpool": POOLING_LAYERS[pname](**params), "whiten": rwhiten, "L": L}
+        pname = "ROIpool"
     head = globalHead(pooling={"name": pname, "params": params}, normal={"name": "L2N", "params": {}}, dim=dim)
     algo = globalFeatureAlgo(loss=None, min_level=0, fpn_levels=1)
     if not whitening:
         algo._head = lambda h, x: h(x, do_whitening=False)
     augment = Normalize(mean, std) if mean is not None else None
     net = ImageRetrievalNet(body, algo, head, augment=augment)
-    net.meta = {"architecture": architecture, "pooling": pooling, "local_whitening": False, "regional": False,
+    net.meta = {"architecture": architecture, "pooling": pooling, "local_whitening": False, "regional": bool(regional),
                 "whitening": whitening, "mean": list(mean) if mean is not None else None,
                 "std": list(std) if std is not None else None, "outputdim": dim}
     return net
@@ -168,8 +177,9 @@ def init_network(params):
     """Upstream ``init_network(params)`` (``scripts/test.py:105``)."""
     arch = params.get("architecture", "resnet101")
     pooling = params.get("pooling", "gem")
-    if params.get("local_whitening", False) or params.get("regional", False):
-        raise NotImplementedError("local whitening / regional pooling are out of scope")
+    if params.get("local_whitening", False):
+        raise NotImplementedError("local_whitening (the per-pixel whitening of upstream cirtorch) is not part of "
+                                  "the reference this engine follows; regional pooling is: regional=True")
     if params.get("pretrained", False):
         # offline build: no ImageNet weights can be fetched; random init instead
         pass
@@ -180,7 +190,8 @@ def init_network(params):
     # descriptor that overflowed fp16's range in bf16.  "bf16" is an explicit
     # opt-in and "fp32" the exact-f32 MFMA parity mode.
     return make_net(arch, pooling, params.get("whitening", False), mean, std,
-                    precision=params.get("precision", "fp16"))
+                    precision=params.get("precision", "fp16"), regional=params.get("regional", False),
+                    regional_whitening=params.get("regional_whitening", True), L=params.get("L", 3))
 
 
 def _load_pil(path, imsize, bbx=None):

@@ -3,7 +3,10 @@
 forward: pool -> L2N -> squeeze -> Linear whiten -> L2N -> permute(1, 0),
 returning a D x N tensor (one column per image).  Pooling is one engine
 launch reading the NHWC stage map once; L2N / Linear / L2N run as the fused
-head tail (``rr_head_l2n_whiten_l2n``).
+head tail (``rr_head_l2n_whiten_l2n``).  ``pooling={"name": "ROIpool",
+"params": {"rpool": ..., "whiten": ..., "L": 3}}`` gives the regional head
+(``Rpool``: state keys ``pool.rpool.p``, ``pool.whiten.*``) and ``{"name":
+"GeMmp", ...}`` per-channel exponents; both pool through ``rr_region_pool``.
 """
 
 import torch.nn as nn
@@ -11,7 +14,7 @@ import torch.nn as nn
 from ... import _ops
 from ...layers import functional as LF
 from ...layers.normalization import L2N
-from ...layers.pooling import GeM, MAC, SPoC
+from ...layers.pooling import GeM, GeMmp, MAC, Rpool, SPoC
 from ..abn import ABN
 from ..normalizations import NORMALIZATION_LAYERS
 from ..pools import POOLING_LAYERS
@@ -47,7 +50,10 @@ class globalHead(nn.Module):
             return _ops.global_pool(x, E.RR_POOL_MAC)
         if isinstance(self.pool, SPoC):
             return _ops.global_pool(x, E.RR_POOL_SPOC)
-        return self.pool(x).squeeze(-1).squeeze(-1)
+        if isinstance(self.pool, (Rpool, GeMmp)):
+            # the regional kernel (Rpool: region vectors already L2N / whitened / aggregated)
+            return self.pool(x).reshape(x.shape[0], -1)
+        raise NotImplementedError("globalHead: pooling module %r" % (self.pool,))
 
     def forward(self, x, do_whitening=True):
         if not isinstance(self.norm, L2N):

@@ -1,22 +1,18 @@
 """Reference path ``cirtorch/modules/pools.py`` (POOLING_LAYERS at :200-207).
 
-GeM / MAC / SPoC run on the engine.  GeMmp, RMAC and ROIpool are out of scope
-for this build (unused by every config, RMAC's region loop is
-mis-indented upstream at ``pools.py:105-113``); they raise on construction.
+GeM / MAC / SPoC / GeMmp and the regional ROIpool (``Rpool``) run on the
+engine.  RMAC keeps raising: upstream its region loop is mis-indented
+(``pools.py:105-113``), so it pools a single region; ``Rpool(MAC())`` is the
+correct R-MAC.
 """
 
-from ..layers.pooling import GeM, MAC, SPoC  # noqa: F401
+from ..layers.pooling import GeM, GeMmp, MAC, Rpool, SPoC  # noqa: F401
 
 
-def _out_of_scope(name):
-    def make(*args, **kwargs):
-        raise NotImplementedError("%s pooling is out of scope for the MI355X engine (see DESIGN.md)" % name)
-    return make
+def RMAC(*args, **kwargs):
+    raise NotImplementedError("RMAC is not built: the upstream region loop is mis-indented (it pools one region "
+                              "only); use Rpool(MAC()) / POOLING_LAYERS['ROIpool'](rpool=MAC()), the correct R-MAC")
 
-
-GeMmp = _out_of_scope("GeMmp")
-RMAC = _out_of_scope("RMAC")
-Rpool = _out_of_scope("ROIpool")
 
 POOLING_LAYERS = {
     "MAC": MAC,

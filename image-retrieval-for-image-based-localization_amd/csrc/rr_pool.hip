@@ -348,6 +348,256 @@ __global__ void __launch_bounds__(256) k_l2n_rows_f64(const double* __restrict__
     for (int i = threadIdx.x; i < dim; i += 256) out[row * dim + i] = (float)(yr[i] / nrm);
 }
 
+// Regional pooling (Rpool.roipool, pools.py:127-172; GeMmp, pools.py:43-54): up
+// to REGION_MAX regions per launch, every pixel of the chunk's bounding box read
+// once.  The region table travels by value in the kernel arguments (256 B).
+// Block = 4 waves over 256 channels: a lane owns 4 channels (one 16-B f32 / 8-B
+// 16-bit load per pixel) and REGION_MAX x 4 statically indexed accumulators;
+// the waves split the pixels of the box (pixel j of the box goes to wave j % 4).
+// A pixel is wave-uniform: lane r < 32 tests it against region r, one ballot
+// gives the 32-bit membership mask in an SGPR, and the fully unrolled region
+// loop branches on its bits (scalar branches: only the regions that contain the
+// pixel cost vector work, the power of GeM is taken once per pixel).  The four
+// per-wave partials are combined through LDS in wave order, so a result depends
+// on nothing but the image and the chunk's table.
+constexpr int REGION_MAX = 32;
+struct RegionTab {
+    rr_region r[REGION_MAX];  // entries past the chunk's count have h == 0 (contain no pixel)
+};
+enum { RK_SPOC = 0, RK_GEM = 1, RK_GEM_PVEC = 2, RK_MAX = 3 };  // GEM: one exponent; GEM_PVEC: one per channel
+
+// one pixel's 4 channels as loaded (8 B of 16-bit values or 16 B of f32), converted when it is pooled
+template <typename T> struct RegionRaw { typedef uint2 type; };
+template <> struct RegionRaw<float> { typedef float4 type; };
+template <typename T>
+__device__ __forceinline__ void region_unpack(const typename RegionRaw<T>::type& q, float* v) {
+    if constexpr (sizeof(T) == 4) {
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+        v[0] = H16<T>::lo(q.x); v[1] = H16<T>::hi(q.x); v[2] = H16<T>::lo(q.y); v[3] = H16<T>::hi(q.y);
+    }
+}
+
+// Waves per SIMD the kernel is compiled for (its VGPR budget: 168 at 3, 256 at 2) and pixels
+// per batch, sized so that two batches of raw pixels fit beside the accumulators (GeM's
+// general power needs the most temporaries; the per-channel form is compiled for 2 waves).
+#ifndef RR_REGION_WAVES
+#define RR_REGION_WAVES 3
+#endif
+constexpr int region_unroll(size_t esz, int kind) {
+    const int regs = (RR_REGION_WAVES >= 3 && kind != RK_GEM_PVEC) ? (kind == RK_GEM ? 4 : 8) : 16;  // per batch
+    return regs / (esz == 4 ? 4 : 2) > 0 ? regs / (esz == 4 ? 4 : 2) : 1;
+}
+
+// x: image 0 of the launch; map row stride W pixels, image stride hw pixels.
+// (by0, bx0, bh, bw): bounding box of the chunk's regions.  out row of region r:
+// (img * R + r0 + r) * c.
+template <typename T, int KIND>
+__global__ void __launch_bounds__(256, KIND == RK_GEM_PVEC ? 2 : RR_REGION_WAVES) k_region_pool(const T* __restrict__ x, int c, int W, long long hw,
+                                                        const RegionTab tab, int nr, int by0, int bx0, int bh, int bw,
+                                                        float p, int ip, const float* __restrict__ pdev, float eps,
+                                                        int R, int r0, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int ch = blockIdx.x * 256 + lane * 4;
+    const bool valid = ch < c;
+    const int chl = valid ? ch : 0;  // lanes past c pool channels 0..3 again and store nothing
+    const long long img = blockIdx.y;
+    __shared__ float part[REGION_MAX][256];
+
+    float p4[4] = {p, p, p, p};
+    if constexpr (KIND == RK_GEM_PVEC) {
+        const float4 q = *reinterpret_cast<const float4*>(pdev + chl);
+        p4[0] = q.x; p4[1] = q.y; p4[2] = q.z; p4[3] = q.w;
+    } else if constexpr (KIND == RK_GEM) {
+        gem_exponent(pdev, p, ip);
+    }
+
+    // lane r holds region r of the table
+    int ry0 = 0, rx0 = 0, rh = 0, rw = 0;
+#pragma unroll
+    for (int r = 0; r < REGION_MAX; ++r) {
+        if (lane == r) {
+            ry0 = tab.r[r].y0; rx0 = tab.r[r].x0; rh = tab.r[r].h; rw = tab.r[r].w;
+        }
+    }
+
+    float acc[REGION_MAX][4];
+#pragma unroll
+    for (int r = 0; r < REGION_MAX; ++r)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[r][k] = KIND == RK_MAX ? -INFINITY : 0.f;
+
+    auto member = [&](int yy, int xx) __attribute__((always_inline)) -> unsigned {
+        const bool in = (unsigned)(yy - ry0) < (unsigned)rh && (unsigned)(xx - rx0) < (unsigned)rw;
+        return (unsigned)__ballot(in);
+    };
+    auto add = [&](const float* v, unsigned m) __attribute__((always_inline)) {
+        float t[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if constexpr (KIND == RK_GEM_PVEC) {
+                // the integer fast paths of powp as selects (the exponent differs per lane)
+                const float b = clamp_min_nan(v[k], eps), b2 = b * b;
+                t[k] = p4[k] == 3.f ? b2 * b : p4[k] == 2.f ? b2 : p4[k] == 1.f ? b : __powf(b, p4[k]);
+            } else if constexpr (KIND == RK_GEM) {
+                t[k] = powp(clamp_min_nan(v[k], eps), p, ip);
+            } else {
+                t[k] = v[k];
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < REGION_MAX; ++r) {
+            if (m & (1u << r)) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[r][k] = KIND == RK_MAX ? max_nan(acc[r][k], t[k]) : acc[r][k] + t[k];
+                // keeps the scalar branch: without it the compiler turns the 32 ifs into
+                // add + select for every region of every pixel (5x the vector work)
+                asm volatile("" : "+v"(acc[r][0]), "+v"(acc[r][1]), "+v"(acc[r][2]), "+v"(acc[r][3]));
+            }
+        }
+    };
+
+    const T* base = x + img * hw * c + chl;
+    const int npx = bh * bw;
+    // box pixel j -> map pixel (by0 + j / bw, bx0 + j % bw), kept incrementally; a wave takes
+    // its pixels wave, wave + 4, ... in batches of UNR.  The loads of batch b + 1 are issued
+    // before batch b is pooled, so a wave always has loads in flight.  A slot past the box's
+    // last pixel reads the box's first pixel with an empty membership mask: every load is
+    // unconditional.
+    typedef typename RegionRaw<T>::type raw_t;
+    constexpr int UNR = region_unroll(sizeof(T), KIND);
+    int j = wave;
+    int yy = by0 + j / bw, xx = bx0 + j % bw;
+    auto fetch = [&](raw_t* q, unsigned* m) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            const bool live = j < npx;
+            const int py = live ? yy : by0, px = live ? xx : bx0;
+            q[u] = *reinterpret_cast<const raw_t*>(base + ((long long)py * W + px) * c);
+            m[u] = live ? member(yy, xx) : 0u;
+            j += 4;
+            xx += 4;
+            while (xx >= bx0 + bw) { xx -= bw; ++yy; }
+        }
+    };
+    const int nbatch = (npx - wave + 4 * UNR - 1) / (4 * UNR);  // npx >= 1: wave 0 has one at least
+    raw_t cur[UNR], nxt[UNR];
+    unsigned mcur[UNR], mnxt[UNR];
+    if (nbatch > 0) fetch(cur, mcur);
+    for (int b = 0; b < nbatch; ++b) {
+        fetch(nxt, mnxt);
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            float v[4];
+            region_unpack<T>(cur[u], v);
+            add(v, mcur[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            cur[u] = nxt[u];
+            mcur[u] = mnxt[u];
+        }
+    }
+
+    // ((wave 0 + wave 1) + wave 2) + wave 3
+    for (int w = 1; w < 4; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int r = 0; r < REGION_MAX; ++r)
+                if (r < nr)
+                    *reinterpret_cast<float4*>(&part[r][lane * 4]) = make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
+        }
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+            for (int r = 0; r < REGION_MAX; ++r)
+                if (r < nr) {
+                    const float4 q = *reinterpret_cast<const float4*>(&part[r][lane * 4]);
+                    const float o[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) acc[r][k] = KIND == RK_MAX ? max_nan(acc[r][k], o[k]) : acc[r][k] + o[k];
+                }
+        }
+        __syncthreads();
+    }
+    // the block finishes the totals (one rolled loop: mean, root, store)
+    if (wave == 0) {
+#pragma unroll
+        for (int r = 0; r < REGION_MAX; ++r)
+            if (r < nr)
+                *reinterpret_cast<float4*>(&part[r][lane * 4]) = make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
+    }
+    __syncthreads();
+    const int cho = blockIdx.x * 256 + (threadIdx.x & 255);
+    if (cho < c) {
+        float pc = p;
+        if constexpr (KIND == RK_GEM_PVEC) pc = pdev[cho];
+        const unsigned short* dims = reinterpret_cast<const unsigned short*>(&tab);  // y0, x0, h, w per region
+        for (int r = 0; r < nr; ++r) {
+            float v = part[r][threadIdx.x];
+            if constexpr (KIND != RK_MAX) v = v / (float)((int)dims[4 * r + 2] * (int)dims[4 * r + 3]);
+            if constexpr (KIND == RK_GEM || KIND == RK_GEM_PVEC) v = __powf(v, 1.0f / pc);
+            out[(img * R + r0 + r) * c + cho] = v;
+        }
+    }
+}
+
+// out[img] = L2N(sum_r rows_r), rows_r = rv[img][r] or its L2N (pools.py:183,195).
+// One block per image; the row norms and the final norm are formed exactly as
+// k_l2n_rows forms them (same thread partition, same order), the sum over the
+// regions runs r = 0 .. R - 1.
+constexpr int AGG_RMAX = 1024;
+__global__ void __launch_bounds__(256) k_region_aggregate(const float* __restrict__ rv, int R, int dim, int l2n,
+                                                          float eps, float* __restrict__ out) {
+    const long long img = blockIdx.x;
+    const float* base = rv + img * R * dim;
+    float* o = out + img * dim;
+    __shared__ float nrm[AGG_RMAX];
+    __shared__ float red[4];
+    if (l2n) {
+        for (int r = 0; r < R; ++r) {
+            const float* xr = base + (long long)r * dim;
+            float ss = 0.f;
+            for (int i = threadIdx.x; i < dim; i += 256) ss += xr[i] * xr[i];
+            ss = wave_sum(ss);
+            if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
+            __syncthreads();
+            if (threadIdx.x == 0) nrm[r] = sqrtf((red[0] + red[1]) + (red[2] + red[3])) + eps;
+            __syncthreads();
+        }
+    }
+    float ss = 0.f;
+    for (int i = threadIdx.x; i < dim; i += 256) {
+        float s = 0.f;
+        for (int r = 0; r < R; ++r) {
+            const float v = base[(long long)r * dim + i];
+            s += l2n ? v / nrm[r] : v;
+        }
+        o[i] = s;  // read back below by the thread that wrote it
+        ss += s * s;
+    }
+    ss = wave_sum(ss);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
+    __syncthreads();
+    const float n2 = sqrtf((red[0] + red[1]) + (red[2] + red[3])) + eps;
+    for (int i = threadIdx.x; i < dim; i += 256) o[i] = o[i] / n2;
+}
+
+template <typename T>
+static void launch_region_pool(int kind, dim3 grid, hipStream_t s, const void* x, int c, int W, long long hw,
+                               const RegionTab& tab, int nr, const int* box, float p, int ip, const float* pdev,
+                               float eps, int R, int r0, float* out) {
+#define RR_REGION_LAUNCH(K)                                                                                          \
+    hipLaunchKernelGGL((k_region_pool<T, K>), grid, dim3(256), 0, s, (const T*)x, c, W, hw, tab, nr, box[0], box[1], \
+                       box[2], box[3], p, ip, pdev, eps, R, r0, out)
+    if (kind == RK_MAX) RR_REGION_LAUNCH(RK_MAX);
+    else if (kind == RK_GEM_PVEC) RR_REGION_LAUNCH(RK_GEM_PVEC);
+    else if (kind == RK_GEM) RR_REGION_LAUNCH(RK_GEM);
+    else RR_REGION_LAUNCH(RK_SPOC);
+#undef RR_REGION_LAUNCH
+}
+
 }  // namespace rr
 
 using namespace rr;
@@ -432,6 +682,74 @@ int rr_head_l2n_whiten_l2n(const float* x, int rows, int dim, const float* w, co
     rc = rr_linear_rows(t0, rows, dim, w, b, dim, t1, stream);
     if (rc) return rc;
     return rr_l2n_rows(t1, rows, dim, eps, y, stream);
+}
+
+int rr_region_pool(const void* x, int n, int h, int w, int c, const rr_region* regions, int R, int mode, float p,
+                   const float* p_dev, int p_count, float eps, float* out, int dtype, void* stream) {
+    if (n <= 0 || h <= 0 || w <= 0 || c <= 0 || R <= 0 || !x || !out || !regions)
+        return fail(RR_EINVAL, "rr_region_pool: empty input");
+    if (h > 65535 || w > 65535) return fail(RR_EINVAL, "rr_region_pool: map larger than 65535");
+    if (mode < 0 || mode > 2) return fail(RR_EINVAL, "rr_region_pool: mode");
+    if (dtype != RR_F32 && dtype != RR_BF16 && dtype != RR_F16) return fail(RR_EINVAL, "rr_region_pool: dtype");
+    if (c % 4) return fail(RR_EINVAL, "rr_region_pool: needs c % 4 == 0");
+    if (((uintptr_t)x & (dtype == RR_F32 ? 15 : 7)) || ((uintptr_t)out & 15))
+        return fail(RR_EINVAL, "rr_region_pool: x must be aligned to 4 channels, out to 16 bytes");
+    for (int r = 0; r < R; ++r) {
+        const rr_region& g = regions[r];
+        if (g.h == 0 || g.w == 0 || (int)g.y0 + g.h > h || (int)g.x0 + g.w > w)
+            return fail(RR_EINVAL, "rr_region_pool: region " + std::to_string(r) + " is empty or outside the map");
+    }
+    int kind = mode == RR_POOL_MAC ? RK_MAX : mode == RR_POOL_GEM ? RK_GEM : RK_SPOC;
+    const float* pdev = nullptr;
+    if (mode == RR_POOL_GEM) {
+        if (p_count == 0) {
+            if (!(p > 0.f)) return fail(RR_EINVAL, "rr_region_pool: GeM p must be > 0");
+        } else if (p_count == 1 || p_count == c) {
+            // a device exponent is read by the kernel
+            if (!p_dev) return fail(RR_EINVAL, "rr_region_pool: p_count > 0 needs p_dev");
+            if (p_count == c && ((uintptr_t)p_dev & 15))
+                return fail(RR_EINVAL, "rr_region_pool: per-channel p_dev must be 16-byte aligned");
+            pdev = p_dev;
+            if (p_count == c) kind = RK_GEM_PVEC;
+        } else {
+            return fail(RR_EINVAL, "rr_region_pool: p_count must be 0, 1 or c");
+        }
+    }
+    const int ip = (p == 3.f) ? 3 : (p == 2.f) ? 2 : (p == 1.f) ? 1 : 0;
+    hipStream_t s = as_stream(stream);
+    const size_t esz = dtype == RR_F32 ? 4 : 2;
+    const long long hw = (long long)h * w;
+    for (int r0 = 0; r0 < R; r0 += REGION_MAX) {
+        const int nr = R - r0 < REGION_MAX ? R - r0 : REGION_MAX;
+        RegionTab tab = {};
+        int y0 = h, x0 = w, y1 = 0, x1 = 0;
+        for (int r = 0; r < nr; ++r) {
+            const rr_region& g = tab.r[r] = regions[r0 + r];
+            y0 = g.y0 < y0 ? g.y0 : y0;
+            x0 = g.x0 < x0 ? g.x0 : x0;
+            y1 = g.y0 + g.h > y1 ? g.y0 + g.h : y1;
+            x1 = g.x0 + g.w > x1 ? g.x0 + g.w : x1;
+        }
+        const int box[4] = {y0, x0, y1 - y0, x1 - x0};
+        for (int i0 = 0; i0 < n; i0 += 65535) {  // grid.y limit
+            const int ni = n - i0 < 65535 ? n - i0 : 65535;
+            const dim3 grid((c + 255) / 256, ni);
+            const void* xi = (const char*)x + (size_t)i0 * hw * c * esz;
+            float* oi = out + (size_t)i0 * R * c;
+            if (dtype == RR_F32) launch_region_pool<float>(kind, grid, s, xi, c, w, hw, tab, nr, box, p, ip, pdev, eps, R, r0, oi);
+            else if (dtype == RR_BF16) launch_region_pool<bf16_t>(kind, grid, s, xi, c, w, hw, tab, nr, box, p, ip, pdev, eps, R, r0, oi);
+            else launch_region_pool<f16_t>(kind, grid, s, xi, c, w, hw, tab, nr, box, p, ip, pdev, eps, R, r0, oi);
+        }
+    }
+    return check_launch("rr_region_pool");
+}
+
+int rr_region_aggregate(const float* rv, int n, int R, int dim, int l2n_rows, float eps, float* out, void* stream) {
+    if (n <= 0 || R <= 0 || dim <= 0 || !rv || !out) return fail(RR_EINVAL, "rr_region_aggregate: empty input");
+    if (R > AGG_RMAX) return fail(RR_EINVAL, "rr_region_aggregate: more than 1024 regions");
+    hipLaunchKernelGGL(k_region_aggregate, dim3(n), dim3(256), 0, as_stream(stream), rv, R, dim, l2n_rows ? 1 : 0, eps,
+                       out);
+    return check_launch("rr_region_aggregate");
 }
 
 size_t rr_whiten_workspace_bytes(int rows, int d_out) { return (size_t)rows * d_out * sizeof(double); }

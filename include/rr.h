@@ -228,6 +228,30 @@ size_t rr_head_workspace_bytes(int rows, int dim);
 int rr_head_l2n_whiten_l2n(const float* x, int rows, int dim, const float* w, const float* b,
                            int whiten, float eps, float* y, void* workspace, void* stream);
 
+/* Regional pooling (R-GeM / R-MAC / R-SPoC): out[n][R][c] float32, one pooled
+ * vector per region of every image, all regions in one pass over the map.
+ * Replaces the per-region loop of Rpool.roipool (cirtorch/modules/pools.py:127-172:
+ * one inner-pool call per narrowed view) and, with the single whole-map region
+ * and per-channel exponents, GeMmp (pools.py:43-54).
+ * x: NHWC [n][h][w][c], c % 4 == 0, any dtype.  regions: R host rectangles inside
+ * the map (copied into the kernel arguments: no device allocation, no host->device
+ * copy, graph-capturable; any R).  GeM exponent by p_count: 0 = the host float p;
+ * 1 = a device scalar p_dev (semantics of rr_global_pool_pdev); c = a device
+ * vector p_dev of one exponent per channel. */
+typedef struct rr_region {
+    uint16_t y0, x0, h, w;
+} rr_region;
+int rr_region_pool(const void* x, int n, int h, int w, int c, const rr_region* regions, int R,
+                   int mode, float p, const float* p_dev, int p_count, float eps, float* out,
+                   int dtype, void* stream);
+
+/* Aggregation of region descriptors: out[n][dim] = L2N(sum_r rv[n][r][:]), eps as
+ * rr_l2n_rows; l2n_rows != 0 first L2-normalises every region row (Rpool without
+ * a whitening layer).  R <= 1024.  Replaces pools.py:183,195 (with a whitening
+ * layer, pools.py:183-187 is rr_head_l2n_whiten_l2n on the n * R rows). */
+int rr_region_aggregate(const float* rv, int n, int R, int dim, int l2n_rows, float eps,
+                        float* out, void* stream);
+
 /* Post-hoc learned whitening, y = L2N(P[:d_out] (x - m)) per row, computed in
  * float64 on the f64 MFMA like the reference (cirtorch/utils/whiten.py:4-12:
  * numpy promotes the float32 vectors to the float64 m, P of whitenlearn;
