@@ -22,6 +22,7 @@ RR_ACT_IDENTITY, RR_ACT_LEAKY = 0, 1
 RR_POOL_GEM, RR_POOL_MAC, RR_POOL_SPOC = 0, 1, 2
 RR_CONV_AFFINE, RR_CONV_RESIDUAL, RR_CONV_PERM32 = 1, 2, 4
 RR_NHWC, RR_NCHW = 0, 1
+RR_MATCH_NN, RR_MATCH_MNN, RR_MATCH_SNN, RR_MATCH_SMNN = 0, 1, 2, 3
 
 _DTYPE_CODE = {torch.float32: RR_F32, torch.bfloat16: RR_BF16, torch.float16: RR_F16,
                torch.int8: RR_I8}  # RR_I8: kNN screening only
@@ -85,6 +86,9 @@ _SIGS = {
     "rr_local_head_workspace_bytes": ([_ll, _i, _i], _sz),
     "rr_local_head": ([_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp], _i),
     "rr_mutual_nn": ([_vp, _i, _vp, _i, _vp, _vp], _i),
+    "rr_match_workspace_bytes": ([_ll, _ll, _i], _sz),
+    "rr_match_top2": ([_vp, _vp, _ll, _vp, _vp, _ll, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp], _i),
+    "rr_match_pairs": ([_vp, _vp, _ll, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _sz, _vp], _i),
     "rr_rank_workspace_bytes": ([_ll, _i], _sz),
     "rr_rank_full": ([_vp, _ll, _vp, _i, _i, _vp, _vp, _sz, _vp], _i),
     "rr_set_tuning": ([_i, _i], _i),

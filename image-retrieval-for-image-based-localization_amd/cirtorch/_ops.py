@@ -642,3 +642,59 @@ def mutual_nn(nn12, nn21):
     out = torch.empty_like(a)
     E.check(E.lib().rr_mutual_nn(E.ptr(a), a.numel(), E.ptr(b), b.numel(), E.ptr(out), _st()), "rr_mutual_nn")
     return out
+
+
+# ---------------------------------------------------------------- batched local matching
+MATCH_MODES = {"nn": E.RR_MATCH_NN, "mnn": E.RR_MATCH_MNN, "snn": E.RR_MATCH_SNN, "smnn": E.RR_MATCH_SMNN}
+
+
+def _match_args(a, a_off, b, b_off, max_n1, max_n2):
+    E.require_gpu(a, a_off, b, b_off)
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise RuntimeError("match: descriptors must be [rows, D] with one D, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or not a.is_contiguous() or not b.is_contiguous():
+        raise RuntimeError("match: descriptors must be contiguous float32 rows")
+    if a_off.dtype != torch.int64 or b_off.dtype != torch.int64 or a_off.numel() != b_off.numel() or a_off.numel() < 1:
+        raise RuntimeError("match: offsets must be int64 [P + 1] for both sides")
+    rows1, rows2 = a.shape[0], b.shape[0]
+    max_n1 = rows1 if max_n1 is None else min(int(max_n1), rows1)
+    max_n2 = rows2 if max_n2 is None else min(int(max_n2), rows2)
+    return rows1, rows2, a_off.numel() - 1, a.shape[1], max_n1, max_n2
+
+
+def match_top2(a, a_off, b, b_off, max_n1=None, max_n2=None):
+    """rr_match_top2: a [rows1, D], b [rows2, D] float32 rows, device int64 offsets [P + 1] ->
+    (d12 float64 [rows1, 2], i12 int32 [rows1, 2], d21 [rows2, 2], i21 [rows2, 2]); rows outside
+    every pair keep (+inf, -1).  No synchronisation."""
+    rows1, rows2, npairs, d, max_n1, max_n2 = _match_args(a, a_off, b, b_off, max_n1, max_n2)
+    dev = a.device
+    d12 = torch.full((rows1, 2), float("inf"), dtype=torch.float64, device=dev)
+    d21 = torch.full((rows2, 2), float("inf"), dtype=torch.float64, device=dev)
+    i12 = torch.full((rows1, 2), -1, dtype=torch.int32, device=dev)
+    i21 = torch.full((rows2, 2), -1, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(E.lib().rr_match_workspace_bytes(rows1, rows2, 0)), dtype=torch.uint8, device=dev)
+    E.check(E.lib().rr_match_top2(E.ptr(a), E.ptr(a_off), rows1, E.ptr(b), E.ptr(b_off), rows2, npairs, d, max_n1,
+                                  max_n2, E.ptr(d12), E.ptr(i12), E.ptr(d21), E.ptr(i21), E.ptr(ws), ws.numel(),
+                                  _st()), "rr_match_top2")
+    return d12, i12, d21, i21
+
+
+def match_pairs(a, a_off, b, b_off, mode, th=0.8, max_n1=None, max_n2=None, covered=False):
+    """rr_match_pairs: -> (match int64 [rows1], dist float32 [rows1]) by the rule of `mode`
+    ("nn", "mnn", "snn", "smnn").  covered=True: the pairs cover every row of a (the outputs are
+    not pre-filled with -1 / inf).  No synchronisation."""
+    if mode not in MATCH_MODES:
+        raise ValueError("match mode %r (one of nn, mnn, snn, smnn)" % (mode,))
+    rows1, rows2, npairs, d, max_n1, max_n2 = _match_args(a, a_off, b, b_off, max_n1, max_n2)
+    dev = a.device
+    if covered and npairs and max_n1:
+        match = torch.empty(rows1, dtype=torch.int64, device=dev)
+        dist = torch.empty(rows1, dtype=torch.float32, device=dev)
+    else:
+        match = torch.full((rows1,), -1, dtype=torch.int64, device=dev)
+        dist = torch.full((rows1,), float("inf"), dtype=torch.float32, device=dev)
+    ws = torch.empty(int(E.lib().rr_match_workspace_bytes(rows1, rows2, 1)), dtype=torch.uint8, device=dev)
+    E.check(E.lib().rr_match_pairs(E.ptr(a), E.ptr(a_off), rows1, E.ptr(b), E.ptr(b_off), rows2, npairs, d, max_n1,
+                                   max_n2, MATCH_MODES[mode], float(th), E.ptr(match), E.ptr(dist), E.ptr(ws),
+                                   ws.numel(), _st()), "rr_match_pairs")
+    return match, dist

@@ -10,6 +10,8 @@
 * ``ShardedIndex``          -> database rows split over the ranks of a
   torch.distributed group (RCCL on ROCm), per-shard top-k, all-gather of the
   (score, index) lists, on-GPU merge — bit-identical to the 1-GPU result.
+* ``match_pairs``           -> local-descriptor matching of P pairs in one launch
+  (nn / mnn / snn / smnn of ``cirtorch/features/matching.py``), no host sync.
 
 Layouts: the reference keeps descriptors as D x N columns; the engine reads
 row-major [N][D].  ``vecs.t()`` of a D x N column matrix produced by
@@ -373,3 +375,57 @@ def mutual_nn(desc1, desc2, precision="fp32"):
     _, n12 = KnnIndex(b, precision).search(a, 1, verify=True)
     _, n21 = KnnIndex(a, precision).search(b, 1, verify=True)
     return _ops.mutual_nn(n12[:, 0], n21[:, 0])
+
+
+def _match_rows(x):
+    """[rows, D] -> contiguous float32 rows with D zero-padded to a multiple of 4
+    (zero columns change no distance)."""
+    x = x.float()
+    if x.shape[1] % 4:
+        x = torch.nn.functional.pad(x, (0, 4 - x.shape[1] % 4))
+    return x.contiguous()
+
+
+def match_pairs(desc1, desc2, mode="mnn", th=0.8, offsets1=None, offsets2=None, max_n1=None, max_n2=None):
+    """Batched local-descriptor matching in one launch (rr_match_pairs): the rules of
+    ``cirtorch/features/matching.py`` -- "nn", "mnn", "snn" (Lowe's ratio test
+    first / second <= th), "smnn" -- for P pairs at once, L2 distances exact to
+    float64 rounding (ties to the lower index), descriptors of any norm,
+    4 <= D <= 512, no N1 x N2 matrix.
+
+    dense   desc1 [P, N1, D] x desc2 [P, N2, D] (or [N1, D] x [N2, D])
+            -> match int64 [P, N1] ([N1]), dist float32 of the same shape
+    ragged  desc1 [rows1, D], desc2 [rows2, D] with device int64 offsets1 / offsets2
+            [P + 1]: pair p is desc1[offsets1[p]:offsets1[p + 1]] against
+            desc2[offsets2[p]:offsets2[p + 1]] -> match, dist [rows1]
+            (max_n1 / max_n2: optional host bounds of a pair's lengths; they
+            only trim the launch grid)
+
+    match[i] is the pair-local index in desc2 or -1, dist[i] the L2 distance
+    (nn, mnn) or the first / second ratio (snn; smnn: the larger of the two
+    directions'), +inf where match is -1.  No device->host synchronisation:
+    graph-capturable (``cirtorch.utils.graph``) for fixed shapes."""
+    if mode not in _ops.MATCH_MODES:
+        raise ValueError("match_pairs: mode %r (one of nn, mnn, snn, smnn)" % (mode,))
+    if (offsets1 is None) != (offsets2 is None):
+        raise ValueError("match_pairs: give both offsets1 and offsets2 (ragged) or neither (dense)")
+    if desc1.shape[-1] != desc2.shape[-1]:
+        raise ValueError("match_pairs: D differs (%d and %d)" % (desc1.shape[-1], desc2.shape[-1]))
+    if not 1 <= desc1.shape[-1] <= 512:
+        raise ValueError("match_pairs: D = %d outside [1, 512]" % desc1.shape[-1])
+    _ops.E.require_gpu(desc1, desc2, offsets1, offsets2)
+    if offsets1 is not None:
+        if desc1.dim() != 2 or desc2.dim() != 2:
+            raise ValueError("match_pairs: the ragged form takes [rows, D] descriptors")
+        return _ops.match_pairs(_match_rows(desc1), offsets1.contiguous(), _match_rows(desc2), offsets2.contiguous(),
+                                mode, th, max_n1, max_n2)
+    if desc1.dim() != desc2.dim() or desc1.dim() not in (2, 3) or (desc1.dim() == 3 and desc1.shape[0] != desc2.shape[0]):
+        raise ValueError("match_pairs: dense descriptors are [P, N, D] or [N, D] on both sides, got %s and %s"
+                         % (tuple(desc1.shape), tuple(desc2.shape)))
+    lead = desc1.shape[:-1]
+    p = desc1.shape[0] if desc1.dim() == 3 else 1
+    n1, n2, d = desc1.shape[-2], desc2.shape[-2], desc1.shape[-1]
+    steps = torch.arange(p + 1, dtype=torch.int64, device=desc1.device)
+    match, dist = _ops.match_pairs(_match_rows(desc1.reshape(p * n1, d)), steps * n1,
+                                   _match_rows(desc2.reshape(p * n2, d)), steps * n2, mode, th, n1, n2, covered=True)
+    return match.view(lead), dist.view(lead)

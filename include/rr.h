@@ -351,6 +351,42 @@ int rr_local_head(const void* x, int n, int h, int w, int c, int dtype, const fl
  * rr_knn_topk with k = 1: exact order, ties -> lower index like np.argmin). */
 int rr_mutual_nn(const long long* nn12, int n1, const long long* nn21, int n2, long long* match, void* stream);
 
+/* Batched local-descriptor matching: cirtorch/features/matching.py:5-154 (match_nn, match_mnn,
+ * match_snn, match_smnn) and, batched, the matcher of HPatchesEval.py:31-43, without the N1 x N2
+ * distance matrix of torch.cdist.  npairs ragged pairs in one launch: side-1 rows of pair p are
+ * a[a_off[p] : a_off[p + 1]], side-2 rows b[b_off[p] : b_off[p + 1]].
+ *   a [rows1][d], b [rows2][d]  float32 rows, 16-byte aligned, any norm; d % 4 == 0, 4 <= d <= 512
+ *   a_off, b_off                DEVICE int64 [npairs + 1], ascending, within [0, rows]
+ *   max_n1, max_n2              host upper bounds of a pair's side lengths (they size the grid;
+ *                               rows1 / rows2 always serve, blocks past a pair's length exit)
+ * rr_match_top2: for every row of both sides the two nearest rows of the pair's other side,
+ *   d12 [rows1][2] float64 squared L2 distances, i12 [rows1][2] int32 pair-local indices in side 2
+ *   (d21 / i21 [rows2][2]: side-2 rows in side 1), ordered by (distance asc, index asc); +inf / -1
+ *   where the other side has fewer than two rows.  d2 = max(0, |a|^2 + |b|^2 - 2 a.b) in float64
+ *   (v_mfma_f64_16x16x4_f64 on the float32 inputs): identical rows tie bit for bit and the lower
+ *   index wins, a row holding a NaN has no neighbour and is nobody's, d12 and d21 hold the same
+ *   bits for the same two rows, and no result depends on npairs or the launch.  Rows outside
+ *   every pair are not written.
+ * rr_match_pairs: rr_match_top2 into the workspace, then the rule of `mode` per side-1 row:
+ *   match [rows1] int64 pair-local index in side 2 or -1, dist [rows1] float32 (+inf where -1);
+ *   s = float32(sqrt(d2)), the value torch.cdist returns, r12 = s(first) / s(second):
+ *     RR_MATCH_NN    nearest row, its distance
+ *     RR_MATCH_MNN   kept when the nearest of match[i] is i; its distance
+ *     RR_MATCH_SNN   kept when r12[i] <= th (Lowe's ratio test); dist = r12[i]
+ *     RR_MATCH_SMNN  both directions pass the ratio test and point at each other;
+ *                    dist = max(r12[i], r21[match[i]])
+ *   SNN / SMNN keep nothing where a side they rank has fewer than two rows.
+ * workspace: rr_match_workspace_bytes(rows1, rows2, lists) with lists = 0 for rr_match_top2,
+ * 1 for rr_match_pairs.  Bad arguments return an error before anything is enqueued. */
+enum rr_match_mode { RR_MATCH_NN = 0, RR_MATCH_MNN = 1, RR_MATCH_SNN = 2, RR_MATCH_SMNN = 3 };
+size_t rr_match_workspace_bytes(long long rows1, long long rows2, int lists);
+int rr_match_top2(const float* a, const long long* a_off, long long rows1, const float* b, const long long* b_off,
+                  long long rows2, int npairs, int d, int max_n1, int max_n2, double* d12, int* i12, double* d21,
+                  int* i21, void* workspace, size_t workspace_bytes, void* stream);
+int rr_match_pairs(const float* a, const long long* a_off, long long rows1, const float* b, const long long* b_off,
+                   long long rows2, int npairs, int d, int max_n1, int max_n2, int mode, float th, long long* match,
+                   float* dist, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Full ranking for any database size: out_idx[q][r] = the r-th database row of
  * query q by (float64 score desc, index asc) — np.argsort(-np.dot(vecs.T, qvecs),
  * axis=0) of scripts/test.py:247-248 as [nq][n] (rr_knn_topk ranks k <= 8192).
