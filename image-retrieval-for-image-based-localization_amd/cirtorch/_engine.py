@@ -89,6 +89,10 @@ _SIGS = {
     "rr_match_workspace_bytes": ([_ll, _ll, _i], _sz),
     "rr_match_top2": ([_vp, _vp, _ll, _vp, _vp, _ll, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp], _i),
     "rr_match_pairs": ([_vp, _vp, _ll, _vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _sz, _vp], _i),
+    "rr_verify_workspace_bytes": ([_ll, _i, _i], _sz),
+    "rr_verify_pairs": ([_vp, _vp, _ll, _vp, _vp, _ll, _vp, _i, _i, _d, _i, _i, ctypes.c_ulonglong, _vp, _vp, _vp, _vp, _sz,
+                         _vp], _i),
+    "rr_homography_dlt": ([_vp, _vp, _vp, _vp, _ll, _i, _vp, _vp, _sz, _vp], _i),
     "rr_rank_workspace_bytes": ([_ll, _i], _sz),
     "rr_rank_full": ([_vp, _ll, _vp, _i, _i, _vp, _vp, _sz, _vp], _i),
     "rr_set_tuning": ([_i, _i], _i),

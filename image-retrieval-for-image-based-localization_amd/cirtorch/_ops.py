@@ -698,3 +698,52 @@ def match_pairs(a, a_off, b, b_off, mode, th=0.8, max_n1=None, max_n2=None, cove
                                    max_n2, MATCH_MODES[mode], float(th), E.ptr(match), E.ptr(dist), E.ptr(ws),
                                    ws.numel(), _st()), "rr_match_pairs")
     return match, dist
+
+
+# ---------------------------------------------------------------- spatial verification
+def verify_pairs(kp1, off1, kp2, off2, match, th=3.0, iters=1024, refine=2, seed=0, max_n1=None, covered=False):
+    """rr_verify_pairs: kp1 [rows1, 2], kp2 [rows2, 2] float32 pixel keypoints, device int64 offsets
+    [P + 1], match int64 [rows1] (rr_match_pairs' output) -> (inliers int32 [P], H float64 [P, 3, 3],
+    mask uint8 [rows1]).  covered=True: the pairs cover every side-1 row (the mask is not
+    pre-filled with 0).  No synchronisation."""
+    E.require_gpu(kp1, off1, kp2, off2, match)
+    if kp1.dim() != 2 or kp2.dim() != 2 or kp1.shape[1] != 2 or kp2.shape[1] != 2:
+        raise RuntimeError("verify: keypoints must be [rows, 2], got %s and %s" % (tuple(kp1.shape), tuple(kp2.shape)))
+    if kp1.dtype != torch.float32 or kp2.dtype != torch.float32 or not kp1.is_contiguous() or not kp2.is_contiguous():
+        raise RuntimeError("verify: keypoints must be contiguous float32 rows")
+    if off1.dtype != torch.int64 or off2.dtype != torch.int64 or off1.numel() != off2.numel() or off1.numel() < 1:
+        raise RuntimeError("verify: offsets must be int64 [P + 1] for both sides")
+    rows1, rows2, npairs = kp1.shape[0], kp2.shape[0], off1.numel() - 1
+    if match.dtype != torch.int64 or match.dim() != 1 or match.shape[0] != rows1 or not match.is_contiguous():
+        raise RuntimeError("verify: match must be contiguous int64 [rows1]")
+    max_n1 = rows1 if max_n1 is None else min(int(max_n1), rows1)
+    dev = kp1.device
+    inliers = torch.empty(npairs, dtype=torch.int32, device=dev)   # written for every pair
+    H = torch.empty((npairs, 3, 3), dtype=torch.float64, device=dev)
+    mask = (torch.empty if covered and npairs else torch.zeros)(rows1, dtype=torch.uint8, device=dev)
+    ws = torch.empty(int(E.lib().rr_verify_workspace_bytes(rows1, npairs, int(iters))), dtype=torch.uint8, device=dev)
+    E.check(E.lib().rr_verify_pairs(E.ptr(kp1), E.ptr(off1), rows1, E.ptr(kp2), E.ptr(off2), rows2, E.ptr(match),
+                                    npairs, max_n1, float(th), int(iters), int(refine),
+                                    int(seed) & 0xFFFFFFFFFFFFFFFF, E.ptr(inliers), E.ptr(H), E.ptr(mask), E.ptr(ws),
+                                    ws.numel(), _st()), "rr_verify_pairs")
+    return inliers, H, mask
+
+
+def homography_dlt(pts1, pts2, weights, off):
+    """rr_homography_dlt: pts1, pts2 float64 [rows, 2], weights float64 [rows] or None, device int64
+    offsets [P + 1] -> H float64 [P, 3, 3] (find_homography_dlt per point set).  No synchronisation."""
+    E.require_gpu(pts1, pts2, weights, off)
+    if pts1.dim() != 2 or pts1.shape[1] != 2 or pts1.shape != pts2.shape:
+        raise RuntimeError("dlt: points must be [rows, 2] on both sides, got %s and %s" % (tuple(pts1.shape), tuple(pts2.shape)))
+    if pts1.dtype != torch.float64 or pts2.dtype != torch.float64 or not pts1.is_contiguous() or not pts2.is_contiguous():
+        raise RuntimeError("dlt: points must be contiguous float64 rows")
+    rows = pts1.shape[0]
+    if weights is not None and (weights.dtype != torch.float64 or weights.shape != (rows,) or not weights.is_contiguous()):
+        raise RuntimeError("dlt: weights must be contiguous float64 [rows]")
+    if off.dtype != torch.int64 or off.numel() < 1:
+        raise RuntimeError("dlt: offsets must be int64 [P + 1]")
+    npairs = off.numel() - 1
+    H = torch.empty((npairs, 3, 3), dtype=torch.float64, device=pts1.device)
+    E.check(E.lib().rr_homography_dlt(E.ptr(pts1), E.ptr(pts2), E.ptr(weights), E.ptr(off), rows, npairs, E.ptr(H),
+                                      E.ptr(None), 0, _st()), "rr_homography_dlt")
+    return H

@@ -429,3 +429,63 @@ def match_pairs(desc1, desc2, mode="mnn", th=0.8, offsets1=None, offsets2=None, 
     match, dist = _ops.match_pairs(_match_rows(desc1.reshape(p * n1, d)), steps * n1,
                                    _match_rows(desc2.reshape(p * n2, d)), steps * n2, mode, th, n1, n2, covered=True)
     return match.view(lead), dist.view(lead)
+
+
+def verify_pairs(kpts1, kpts2, match, th=3.0, iters=1024, refine=2, seed=0, offsets1=None, offsets2=None, max_n1=None):
+    """Spatial verification of matched pairs in one call (rr_verify_pairs): per pair a RANSAC
+    homography over the kept matches (``match[i] >= 0``), refitted `refine` times by the
+    reference's DLT on its inliers -- what ``compute_H_estimation`` (HPatchesEval.py:45-69) gets
+    from ``cv2.findHomography(..., cv2.RANSAC)`` one pair at a time on the host.  float64 on
+    float32 pixel keypoints (x, y); `iters` hypotheses per pair drawn by a counter hash of
+    (seed, pair, t), so a result is bit-identical run to run and does not depend on the batch.
+
+    dense   kpts1 [P, N1, 2], kpts2 [P, N2, 2], match int64 [P, N1] (or [N1, 2], [N2, 2], [N1])
+            -> inliers int32 [P], H float64 [P, 3, 3], mask bool [P, N1]
+    ragged  kpts1 [rows1, 2], kpts2 [rows2, 2], match [rows1] with device int64 offsets1 /
+            offsets2 [P + 1], the tables given to ``match_pairs`` -> inliers [P], H [P, 3, 3],
+            mask [rows1] (max_n1: optional host bound of a pair's side-1 length)
+
+    `match` is exactly what ``match_pairs`` returns.  inliers counts the matches within `th`
+    pixels of H, mask marks their side-1 rows; a pair with fewer than 4 matches or only degenerate
+    samples gives 0, an all-zero H and an empty mask.  No device->host synchronisation:
+    graph-capturable for fixed shapes."""
+    if (offsets1 is None) != (offsets2 is None):
+        raise ValueError("verify_pairs: give both offsets1 and offsets2 (ragged) or neither (dense)")
+    if kpts1.shape[-1] != 2 or kpts2.shape[-1] != 2:
+        raise ValueError("verify_pairs: keypoints are (x, y) rows, got %s and %s" % (tuple(kpts1.shape), tuple(kpts2.shape)))
+    if int(iters) < 1 or int(refine) < 0 or not (float(th) > 0.0 and float(th) < float("inf")):
+        raise ValueError("verify_pairs: iters >= 1, refine >= 0 and a positive finite th, got %r, %r, %r" % (iters, refine, th))
+    if match.dtype != torch.int64:
+        raise ValueError("verify_pairs: match must be int64 (the output of match_pairs), got %s" % match.dtype)
+    if offsets1 is not None:
+        if kpts1.dim() != 2 or kpts2.dim() != 2 or match.dim() != 1 or match.shape[0] != kpts1.shape[0]:
+            raise ValueError("verify_pairs: the ragged form takes [rows, 2] keypoints and match [rows1]")
+        _ops.E.require_gpu(kpts1, kpts2, match, offsets1, offsets2)
+        inl, H, mask = _ops.verify_pairs(kpts1.float().contiguous(), offsets1.contiguous(), kpts2.float().contiguous(),
+                                         offsets2.contiguous(), match.contiguous(), th, iters, refine, seed, max_n1)
+        return inl, H, mask.view(torch.bool)
+    if kpts1.dim() != kpts2.dim() or kpts1.dim() not in (2, 3) or (kpts1.dim() == 3 and kpts1.shape[0] != kpts2.shape[0]) \
+            or tuple(match.shape) != tuple(kpts1.shape[:-1]):
+        raise ValueError("verify_pairs: dense keypoints are [P, N, 2] or [N, 2] on both sides with match [P, N1] or [N1], "
+                         "got %s, %s and %s" % (tuple(kpts1.shape), tuple(kpts2.shape), tuple(match.shape)))
+    p = kpts1.shape[0] if kpts1.dim() == 3 else 1
+    n1, n2 = kpts1.shape[-2], kpts2.shape[-2]
+    if max_n1 is not None and int(max_n1) < n1:
+        raise ValueError("verify_pairs: max_n1 = %d below the pairs' length %d" % (int(max_n1), n1))
+    _ops.E.require_gpu(kpts1, kpts2, match)
+    steps = torch.arange(p + 1, dtype=torch.int64, device=kpts1.device)
+    inl, H, mask = _ops.verify_pairs(kpts1.float().reshape(p * n1, 2).contiguous(), steps * n1,
+                                     kpts2.float().reshape(p * n2, 2).contiguous(), steps * n2,
+                                     match.reshape(p * n1).contiguous(), th, iters, refine, seed, n1, covered=True)
+    return inl, H, mask.view(torch.bool).view(match.shape)
+
+
+def rerank_by_inliers(idx, inliers):
+    """Re-order a [k, Q] shortlist (``knn``'s ranks: column q lists query q's database rows, best
+    first) by the verified inlier counts [k, Q] of its entries: (inliers desc, original rank
+    asc).  Plain torch (a stable sort), works on any device, no host synchronisation."""
+    if idx.dim() != 2 or tuple(inliers.shape) != tuple(idx.shape):
+        raise ValueError("rerank_by_inliers: idx and inliers must both be [k, Q], got %s and %s"
+                         % (tuple(idx.shape), tuple(inliers.shape)))
+    order = torch.sort(inliers.to(torch.int64), dim=0, descending=True, stable=True).indices
+    return torch.gather(idx, 0, order)

@@ -387,6 +387,70 @@ int rr_match_pairs(const float* a, const long long* a_off, long long rows1, cons
                    long long rows2, int npairs, int d, int max_n1, int max_n2, int mode, float th, long long* match,
                    float* dist, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Spatial verification of matched pairs: a RANSAC homography per pair, its inlier count and
+ * mask.  Replaces, batched and without a host round trip, the per-pair
+ * cv2.findHomography(kp1[matches], kp2[matches], cv2.RANSAC) of
+ * cirtorch/utils/evaluation/HPatchesEval.py:45-69 (compute_H_estimation) and refits with
+ * find_homography_dlt of cirtorch/geometry/homography.py:11-58.  (It is not OpenCV's RANSAC bit
+ * for bit: the sampling, the stopping rule and the refit are the ones stated here.)
+ *   kp1 [rows1][2], kp2 [rows2][2]  float32 pixel keypoints (x, y), 8-byte aligned
+ *   off1, off2                      DEVICE int64 [npairs + 1], the tables of rr_match_pairs
+ *   match [rows1]                   int64, what rr_match_pairs wrote: the pair-local side-2 index
+ *                                   or -1 (an index outside the pair's side 2 counts as -1)
+ *   max_n1                          host upper bound of a pair's side-1 length, <= rows1; rows of
+ *                                   a pair past max_n1 are ignored
+ * All arithmetic is float64, every sum has a fixed order: results are bit-identical run to run
+ * and do not depend on npairs or the launch.  Per pair p:
+ *  a. records: the kept rows i (match[i] >= 0) in ascending i as (x1, y1, x2, y2); M of them.
+ *  b. hypothesis t in [0, iters): four distinct record indices from a counter hash.  With
+ *       mix(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16
+ *     on uint32 (wrapping),
+ *       s = mix(lo32(seed) + 0x9e3779b9);  s = mix(s ^ hi32(seed));  s = mix(s + p);  s = mix(s + t)
+ *     and a = [0, 1, ..., M - 1]:  for j = 0, 1, 2, 3:
+ *       k = mix(s + j) mod (M - j);  sample_j = a[k];  a[k] = a[M - 1 - j]
+ *     (a partial Fisher-Yates draw over the M - j records that remain).  The homography through
+ *     the four records, scaled to H[2][2] = 1.  The hypothesis is degenerate and scores 0 when,
+ *     on either side, the determinant [[xa, xb, xc], [ya, yb, yc], [1, 1, 1]] =
+ *     (xb - xa)(yc - ya) - (xc - xa)(yb - ya) of any three of its four points has magnitude
+ *     <= RR_VERIFY_DET_EPS (px^2: twice a triangle's area; the float64 rounding of that
+ *     expression on coordinates below 2^11 is below 1e-9), or an entry of H is not finite.
+ *  c. score: the number of records with |w| > 1e-8 and (u - x2 w)^2 + (v - y2 w)^2 <= th^2 w^2,
+ *     (u, v, w) = H [x1, y1, 1] -- that is || pi(H x1) - x2 ||^2 <= th^2 without the division.
+ *     The winner is the hypothesis of the highest score, the lowest t among equals.
+ *  d. refit, `refine` times: S = the inliers of H; H' = find_homography_dlt on S (unweighted:
+ *     normalize_points on both sides, A^T A of the rows of homography.py:32-33, the eigenvector
+ *     of its smallest eigenvalue by cyclic Jacobi, T2^-1 h T1, divided by H[2][2] + 1e-8);
+ *     H' replaces H when it is finite and score(H') >= score(H), otherwise the refit stops.
+ *  e. inliers[p] = score(H), H [npairs][3][3] float64 row-major, mask [rows1] uint8 = 1 on the
+ *     side-1 rows that are inliers of H (every row of the pair is written).  M < 4 or no
+ *     hypothesis with a score above 0: inliers 0, H all zeros, mask 0.
+ * workspace: rr_verify_workspace_bytes(rows1, npairs, iters).  Nothing waits for the host
+ * (graph-capturable).  Bad arguments (null pointers, iters < 1, refine < 0, th <= 0 or not finite,
+ * max_n1 > rows1, a short workspace) return an error before anything is enqueued; npairs == 0
+ * returns RR_OK and launches nothing. */
+#define RR_VERIFY_DET_EPS 1e-6
+size_t rr_verify_workspace_bytes(long long rows1, int npairs, int iters);
+int rr_verify_pairs(const float* kp1, const long long* off1, long long rows1, const float* kp2, const long long* off2,
+                    long long rows2, const long long* match, int npairs, int max_n1, double th, int iters, int refine,
+                    unsigned long long seed, int* inliers, double* H, unsigned char* mask, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* Batched weighted DLT: find_homography_dlt of cirtorch/geometry/homography.py:11-58 (and the
+ * solver inside find_homography_dlt_iterated, :61-74) with normalize_points of
+ * cirtorch/geometry/epipolar/fundamental.py:6-33, for npairs ragged point sets in one launch; the
+ * device routine of step d above.
+ *   pts1, pts2 [rows][2]  float64 (x, y), 16-byte aligned; set p is rows off[p] .. off[p + 1]
+ *   weights [rows]        float64 or NULL (unweighted); they weigh the two rows of a point in
+ *                         A^T W A, the normalisation is over all points of the set
+ *   off                   DEVICE int64 [npairs + 1]
+ *   H [npairs][3][3]      float64; all zeros for a set of fewer than 4 points
+ * sqrt(2) of normalize_points is the float32 value the reference's torch.sqrt(torch.tensor(2.))
+ * yields.  The eigenvector comes from cyclic Jacobi on the 9 x 9 matrix, rotations skipped where
+ * |a_pq| <= 2^-52 sqrt(a_pp a_qq), until a sweep rotates nothing (the reference: the last right
+ * singular vector of torch.svd; the sign cancels in the division).
+ * workspace: none is needed (NULL, 0); the arguments are reserved. */
+int rr_homography_dlt(const double* pts1, const double* pts2, const double* weights, const long long* off,
+                      long long rows, int npairs, double* H, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Full ranking for any database size: out_idx[q][r] = the r-th database row of
  * query q by (float64 score desc, index asc) — np.argsort(-np.dot(vecs.T, qvecs),
  * axis=0) of scripts/test.py:247-248 as [nq][n] (rr_knn_topk ranks k <= 8192).
