@@ -23,6 +23,7 @@ RR_POOL_GEM, RR_POOL_MAC, RR_POOL_SPOC = 0, 1, 2
 RR_CONV_AFFINE, RR_CONV_RESIDUAL, RR_CONV_PERM32 = 1, 2, 4
 RR_NHWC, RR_NCHW = 0, 1
 RR_MATCH_NN, RR_MATCH_MNN, RR_MATCH_SNN, RR_MATCH_SMNN = 0, 1, 2, 3
+RR_RESP_HARRIS, RR_RESP_GFTT, RR_RESP_HESSIAN = 0, 1, 2
 
 _DTYPE_CODE = {torch.float32: RR_F32, torch.bfloat16: RR_BF16, torch.float16: RR_F16,
                torch.int8: RR_I8}  # RR_I8: kNN screening only
@@ -93,6 +94,12 @@ _SIGS = {
     "rr_verify_pairs": ([_vp, _vp, _ll, _vp, _vp, _ll, _vp, _i, _i, _d, _i, _i, ctypes.c_ulonglong, _vp, _vp, _vp, _vp, _sz,
                          _vp], _i),
     "rr_homography_dlt": ([_vp, _vp, _vp, _vp, _ll, _i, _vp, _vp, _sz, _vp], _i),
+    "rr_detect_workspace_bytes": ([_i, _i, _i, _i], _sz),
+    "rr_response": ([_vp, _i, _i, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp], _i),
+    "rr_nms2d": ([_vp, _ll, _i, _i, _i, _i, _vp, _vp], _i),
+    "rr_select_keypoints": ([_vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp], _i),
+    "rr_detect_keypoints": ([_vp, _i, _i, _i, _i, _i, _i, _d, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz,
+                             _vp], _i),
     "rr_rank_workspace_bytes": ([_ll, _i], _sz),
     "rr_rank_full": ([_vp, _ll, _vp, _i, _i, _vp, _vp, _sz, _vp], _i),
     "rr_set_tuning": ([_i, _i], _i),

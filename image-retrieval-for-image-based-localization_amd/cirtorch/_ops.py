@@ -747,3 +747,114 @@ def homography_dlt(pts1, pts2, weights, off):
     E.check(E.lib().rr_homography_dlt(E.ptr(pts1), E.ptr(pts2), E.ptr(weights), E.ptr(off), rows, npairs, E.ptr(H),
                                       E.ptr(None), 0, _st()), "rr_homography_dlt")
     return H
+
+
+# ---------------------------------------------------------------- keypoint detection
+RESPONSES = {"harris": E.RR_RESP_HARRIS, "gftt": E.RR_RESP_GFTT, "hessian": E.RR_RESP_HESSIAN}
+NMS_SIZES = (3, 5, 7, 9)
+
+
+def _detect_input(x, what):
+    E.require_gpu(x)
+    if x.dim() != 4:
+        raise ValueError("%s: expected [B, C, H, W], got %s" % (what, tuple(x.shape)))
+    if x.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("%s: images are float32 or uint8, got %s" % (what, x.dtype))
+    if x.shape[2] < 4 or x.shape[3] < 4:
+        raise ValueError("%s: H and W must be at least 4, got %s" % (what, tuple(x.shape)))
+    return x.contiguous()
+
+
+def _detect_sigmas(sigmas, n):
+    if sigmas is None:
+        return None
+    E.require_gpu(sigmas)
+    if sigmas.dim() != 1 or sigmas.shape[0] != n:
+        raise ValueError("sigmas must be [B], got %s" % (tuple(sigmas.shape),))
+    return sigmas.float().contiguous()
+
+
+def response(x, kind, k=0.04, sigmas=None, gray=False):
+    """rr_response: x [B, C, H, W] float32 or uint8 -> float32 scores [B, C, H, W] (gray=True:
+    C == 3 reduced to gray first, [B, 1, H, W]).  kind: "harris" (with k), "gftt", "hessian".
+    No synchronisation."""
+    if kind not in RESPONSES:
+        raise ValueError("response %r (one of harris, gftt, hessian)" % (kind,))
+    x = _detect_input(x, "response")
+    n, c, h, w = x.shape
+    if gray and c != 3:
+        raise ValueError("response: gray needs C == 3, got %d" % c)
+    sg = _detect_sigmas(sigmas, n)
+    out = torch.empty((n, 1 if gray else c, h, w), dtype=torch.float32, device=x.device)
+    E.check(E.lib().rr_response(E.ptr(x), n, c, h, w, int(x.dtype == torch.uint8), int(bool(gray)), RESPONSES[kind],
+                                float(k), E.ptr(sg), E.ptr(out), _st()), "rr_response")
+    return out
+
+
+def nms2d(x, ks, mask_only=False):
+    """rr_nms2d: float32 planes [..., H, W], square window ks in (3, 5, 7, 9) -> bool mask or
+    x * mask of the same shape.  No synchronisation."""
+    E.require_gpu(x)
+    if x.dim() < 2 or x.dtype != torch.float32:
+        raise RuntimeError("nms2d: float32 planes [..., H, W], got %s %s" % (x.dtype, tuple(x.shape)))
+    if ks not in NMS_SIZES:
+        raise ValueError("nms2d: window %r (one of 3, 5, 7, 9)" % (ks,))
+    x = x.contiguous()
+    h, w = x.shape[-2:]
+    planes = x.numel() // (h * w) if h * w else 0
+    out = torch.empty(x.shape, dtype=torch.uint8 if mask_only else torch.float32, device=x.device)
+    E.check(E.lib().rr_nms2d(E.ptr(x), planes, h, w, int(ks), int(bool(mask_only)), E.ptr(out), _st()), "rr_nms2d")
+    return out.view(torch.bool) if mask_only else out
+
+
+def _select_args(num, ks, min_score, border):
+    if ks not in NMS_SIZES:
+        raise ValueError("keypoints: nms window %r (one of 3, 5, 7, 9)" % (ks,))
+    if not 1 <= int(num) <= 8192:
+        raise ValueError("keypoints: num_features = %r outside [1, 8192]" % (num,))
+    if int(border) < 0 or float(min_score) != float(min_score):
+        raise ValueError("keypoints: border >= 0 and a min_score that is not NaN, got %r, %r" % (border, min_score))
+
+
+def select_keypoints(score, num, ks=5, min_score=0.0, border=0):
+    """rr_select_keypoints: score [B, H, W] float32 -> (kpts float32 [B, num, 2] pixel (x, y), scores
+    float32 [B, num], count int32 [B]); the slots past count hold (-1, -1) and 0.  No synchronisation."""
+    E.require_gpu(score)
+    if score.dim() != 3 or score.dtype != torch.float32:
+        raise RuntimeError("select_keypoints: score must be float32 [B, H, W], got %s %s" % (score.dtype, tuple(score.shape)))
+    _select_args(num, ks, min_score, border)
+    score = score.contiguous()
+    n, h, w = score.shape
+    dev = score.device
+    kpts = torch.empty((n, num, 2), dtype=torch.float32, device=dev)
+    scores = torch.empty((n, num), dtype=torch.float32, device=dev)
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(E.lib().rr_detect_workspace_bytes(n, h, w, int(num))), dtype=torch.uint8, device=dev)
+    E.check(E.lib().rr_select_keypoints(E.ptr(score), n, h, w, int(ks), int(num), float(min_score), int(border),
+                                        E.ptr(kpts), E.ptr(scores), E.ptr(count), E.ptr(ws), ws.numel(), _st()),
+            "rr_select_keypoints")
+    return kpts, scores, count
+
+
+def detect_keypoints(x, num, kind="harris", k=0.04, ks=5, min_score=0.0, border=0, sigmas=None, return_response=False):
+    """rr_detect_keypoints: x [B, 1|3, H, W] float32 or uint8 -> (kpts, scores, count) as
+    select_keypoints, plus the score map [B, 1, H, W] on request.  No synchronisation."""
+    if kind not in RESPONSES:
+        raise ValueError("response %r (one of harris, gftt, hessian)" % (kind,))
+    x = _detect_input(x, "detect_keypoints")
+    n, c, h, w = x.shape
+    if c not in (1, 3):
+        raise ValueError("detect_keypoints: images are [B, 1, H, W] or [B, 3, H, W], got C = %d" % c)
+    _select_args(num, ks, min_score, border)
+    sg = _detect_sigmas(sigmas, n)
+    dev = x.device
+    kpts = torch.empty((n, num, 2), dtype=torch.float32, device=dev)
+    scores = torch.empty((n, num), dtype=torch.float32, device=dev)
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    smap = torch.empty((n, 1, h, w), dtype=torch.float32, device=dev) if return_response else None
+    ws = torch.empty(int(E.lib().rr_detect_workspace_bytes(n, h, w, int(num))), dtype=torch.uint8, device=dev)
+    E.check(E.lib().rr_detect_keypoints(E.ptr(x), n, c, h, w, int(x.dtype == torch.uint8), RESPONSES[kind], float(k),
+                                        E.ptr(sg), int(ks), int(num), float(min_score), int(border), E.ptr(kpts),
+                                        E.ptr(scores), E.ptr(count), E.ptr(smap), E.ptr(ws), ws.numel(), _st()),
+            "rr_detect_keypoints")
+    return (kpts, scores, count, smap) if return_response else (kpts, scores, count)

@@ -12,6 +12,8 @@
   (score, index) lists, on-GPU merge — bit-identical to the 1-GPU result.
 * ``match_pairs``           -> local-descriptor matching of P pairs in one launch
   (nn / mnn / snn / smnn of ``cirtorch/features/matching.py``), no host sync.
+* ``detect_keypoints``      -> the best N corners / blobs of every image of a batch (response,
+  non-maxima suppression and top-N selection on the device), no host sync.
 
 Layouts: the reference keeps descriptors as D x N columns; the engine reads
 row-major [N][D].  ``vecs.t()`` of a D x N column matrix produced by
@@ -375,6 +377,39 @@ def mutual_nn(desc1, desc2, precision="fp32"):
     _, n12 = KnnIndex(b, precision).search(a, 1, verify=True)
     _, n21 = KnnIndex(a, precision).search(b, 1, verify=True)
     return _ops.mutual_nn(n12[:, 0], n21[:, 0])
+
+
+def detect_keypoints(images, num_features=2048, response="harris", k=0.04, nms=5, min_score=0.0, border=0, sigmas=None,
+                     return_response=False):
+    """Keypoints of a batch of images in one call (rr_detect_keypoints): the Harris, Shi-Tomasi
+    ("gftt") or Hessian response of ``cirtorch/features/responses.py`` on the gray image, the
+    ``nms x nms`` non-maxima suppression of ``cirtorch/features/nms.py`` and the `num_features`
+    best maxima by (score desc, y * W + x asc) -- the device-side replacement of the host
+    detector ``generate_kpts(..., 'sift')`` (``cirtorch/datasets/localFeatures/utils.py:56-99``).
+
+    images  [B, 1|3, H, W], float32 in [0, 1] or uint8 (a pixel is v / 255); three channels are
+            reduced by 0.299 r + 0.587 g + 0.114 b
+    ->      kpts float32 [B, N, 2] pixel (x, y) (the layout ``verify_pairs`` takes), scores float32
+            [B, N], count int32 [B]; the slots past count hold (-1, -1) and score 0.  With
+            return_response=True also the score map float32 [B, 1, H, W].
+
+    A candidate is a positive strict maximum of its window with score > min_score, at least
+    `border` pixels from every edge.  float64 arithmetic rounded once: the result is
+    bit-identical run to run and does not depend on the batch.  No device->host
+    synchronisation: graph-capturable for fixed shapes."""
+    if response not in _ops.RESPONSES:
+        raise ValueError("detect_keypoints: response %r (one of harris, gftt, hessian)" % (response,))
+    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] not in (1, 3):
+        raise ValueError("detect_keypoints: images are [B, 1, H, W] or [B, 3, H, W], got %s"
+                         % (tuple(images.shape) if torch.is_tensor(images) else type(images),))
+    if images.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("detect_keypoints: images are float32 or uint8, got %s" % images.dtype)
+    if isinstance(nms, tuple):
+        if len(nms) != 2 or nms[0] != nms[1]:
+            raise ValueError("detect_keypoints: the nms window must be square, got %r" % (nms,))
+        nms = nms[0]
+    return _ops.detect_keypoints(images, int(num_features), response, float(k), nms, float(min_score), int(border),
+                                 sigmas, return_response)
 
 
 def _match_rows(x):

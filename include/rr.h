@@ -451,6 +451,81 @@ int rr_verify_pairs(const float* kp1, const long long* off1, long long rows1, co
 int rr_homography_dlt(const double* pts1, const double* pts2, const double* weights, const long long* off,
                       long long rows, int npairs, double* H, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Keypoint detection (rr_detect.hip): corner / blob responses, 2-D non-maxima suppression and the
+ * best N local maxima per image.  Replaces harris_response, gftt_response and hessian_response of
+ * cirtorch/features/responses.py:8-103 (spatial_gradient of cirtorch/filters/sobel.py:12-45,
+ * gaussian_blur2d of cirtorch/filters/gaussian.py:8-16, filter2D of cirtorch/filters/filter.py:34-77),
+ * rgb_to_grayscale of cirtorch/enhance/color/gray.py:7-25, nms2d of cirtorch/features/nms.py:29-67
+ * and the torch.topk(x * mask) after it -- and with them the host-side cv2 SIFT detector of
+ * cirtorch/datasets/localFeatures/utils.py:56-99.  The image is read once (apart from tile halos)
+ * and the score written once: no gradient, product or blurred plane ever exists in memory.
+ *
+ * The response of a plane.  x [n][c][h][w] float32, or uint8 with u8 = 1 (a pixel is then
+ * float32(v) / 255.0f in IEEE float32, so the result has the bits of the float32 path fed
+ * x.float() / 255).  gray = 0: each of the n c planes is scored on its own, out [n][c][h][w];
+ * gray = 1: c must be 3, a pixel is (0.299 r + 0.587 g) + 0.114 b and out is [n][1][h][w].
+ * With p(y, x) the pixel at clamped coordinates (replicate padding):
+ *   dx = ((p(y-1,x+1) - p(y-1,x-1)) + 2 (p(y,x+1) - p(y,x-1)) + (p(y+1,x+1) - p(y+1,x-1))) / 8
+ *   dy = ((p(y+1,x-1) - p(y-1,x-1)) + 2 (p(y+1,x) - p(y-1,x)) + (p(y+1,x+1) - p(y-1,x+1))) / 8
+ * (the 3 x 3 Sobel pair / 8 as a correlation: dx > 0 where the right neighbour is larger),
+ *   A = G * dx^2,  B = G * dy^2,  C = G * (dx dy),  det = A B - C C,  tr = A + B
+ * with G the 7 x 7 Gaussian of sigma 1 applied separably (along x, then along y, taps in ascending
+ * offset; the seven weights are the float32 values of get_gaussian_kernel1d(7, 1.0)) on reflected
+ * coordinates (-i reads i, h - 1 + i reads h - 1 - i; the edge sample is not repeated), and
+ *   RR_RESP_HARRIS   det - k tr^2
+ *   RR_RESP_GFTT     0.5 (tr - sqrt(|tr^2 - 4 det|))
+ *   RR_RESP_HESSIAN  dxx dyy - dxy^2, the 5 x 5 second-order Sobel kernels gxx, gxy, gyy as
+ *                    correlations over clamped coordinates (rows, then columns, ascending), divided
+ *                    by the sums of their magnitudes 64, 36, 64 (1 / 36 as its float32 value, which
+ *                    is what the reference's normalised kernel holds).
+ * sigmas: NULL or DEVICE float32 [n]; the score of every plane of image i is multiplied by
+ * sigma_i^4 = (s s)(s s).  All arithmetic is float64 in one fixed order per pixel and each score is
+ * rounded once to float32: a score depends on the pixels of its window only, not on n, the tile,
+ * the launch or the run.  Only sobel gradients (grads_mode = 'sobel') exist.
+ * Errors, before anything is enqueued: null x or out, c < 1, h or w below 4 (what the reference's
+ * reflect padding accepts), gray not 0 / 1 or gray with c != 3, an unknown kind, a non-finite k for
+ * Harris, more than 2^31 pixels.  n == 0 returns RR_OK and launches nothing.  Nothing waits for the
+ * host (graph-capturable). */
+#define RR_RESP_HARRIS 0
+#define RR_RESP_GFTT 1
+#define RR_RESP_HESSIAN 2
+int rr_response(const void* x, int n, int c, int h, int w, int u8, int gray, int kind, double k, const float* sigmas,
+                float* out, void* stream);
+/* 2-D non-maxima suppression of float32 planes x [planes][h][w] with a square window ks in
+ * {3, 5, 7, 9}.  A pixel is kept when its value is greater than 0 and strictly greater than every
+ * other position of the window; window coordinates are clamped to the map and a clamped neighbour
+ * that lands on the centre still counts, so a pixel on the map's edge is never kept; NaN is never
+ * kept.  (The comparison with 0 is the reference's: the centre filter of _get_nms_kernel2d,
+ * nms.py:6-15, is all zeros, so its maximum over the other positions includes 0 and it keeps no
+ * maximum that is not positive.)  out: mask_only = 1 a uint8 mask [planes][h][w], else x * mask as
+ * float32.  Pure comparisons: the result equals the reference's on finite maps bit for bit.
+ * Errors: null x or out, a bad ks, h or w < 1, more than 2^31 pixels.  planes == 0 returns RR_OK.
+ * Nothing waits for the host. */
+int rr_nms2d(const float* x, long long planes, int h, int w, int ks, int mask_only, void* out, void* stream);
+/* The best num local maxima of one score plane per image, score [n][h][w] float32.  Candidates are
+ * the pixels the NMS rule above keeps for ks whose score is > min_score and which lie at least
+ * `border` pixels from every edge (border <= x < w - border, likewise y).  The num best by (score
+ * descending, y w + x ascending) go to
+ *   kpts [n][num][2] float32 pixel (x, y) -- the layout rr_verify_pairs takes --,
+ *   scores [n][num] float32, count [n] int32;
+ * the slots past count hold (-1, -1) and score 0.  1 <= num <= 8192.  No two 8-neighbours are both
+ * strict maxima, so an image has at most ceil(h / 2) ceil(w / 2) candidates; the workspace
+ * (rr_detect_workspace_bytes(n, h, w, num)) is sized by that bound and cannot overflow.  Candidates
+ * are compacted with integer atomics in any order; their keys (score bits, index) are unique per
+ * image, so the selected set and its order are fully determined.
+ * Errors: null pointers, a bad ks, num, h or w, a negative border, a NaN min_score, more than 2^31
+ * pixels, a short workspace (RR_ENOSPACE).  n == 0 returns RR_OK.  Nothing waits for the host. */
+size_t rr_detect_workspace_bytes(int n, int h, int w, int num);
+int rr_select_keypoints(const float* score, int n, int h, int w, int ks, int num, float min_score, int border, float* kpts,
+                        float* scores, int* count, void* workspace, size_t workspace_bytes, void* stream);
+/* The response of x [n][c][h][w] (c = 1, or c = 3 reduced to gray), written to score_map
+ * [n][1][h][w] (or, when score_map is NULL, into the workspace), then the selection above on the
+ * same stream: bit-identical to calling the two entries one after the other.  Errors: those of the
+ * two entries and c not 1 or 3.  n == 0 returns RR_OK.  Nothing waits for the host. */
+int rr_detect_keypoints(const void* x, int n, int c, int h, int w, int u8, int kind, double k, const float* sigmas, int ks,
+                        int num, float min_score, int border, float* kpts, float* scores, int* count, float* score_map,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* Full ranking for any database size: out_idx[q][r] = the r-th database row of
  * query q by (float64 score desc, index asc) — np.argsort(-np.dot(vecs.T, qvecs),
  * axis=0) of scripts/test.py:247-248 as [nq][n] (rr_knn_topk ranks k <= 8192).
