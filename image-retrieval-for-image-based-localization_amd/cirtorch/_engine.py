@@ -100,6 +100,12 @@ _SIGS = {
     "rr_select_keypoints": ([_vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp], _i),
     "rr_detect_keypoints": ([_vp, _i, _i, _i, _i, _i, _i, _d, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz,
                              _vp], _i),
+    "rr_describe_workspace_bytes": ([_i, _i, _i, _i, _i], _sz),
+    "rr_extract_patches": ([_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp], _i),
+    "rr_patch_orientation": ([_vp, _ll, _i, _i, _vp, _vp], _i),
+    "rr_sift_describe": ([_vp, _ll, _i, _i, _i, _i, _d, _vp, _vp], _i),
+    "rr_describe_keypoints": ([_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _d, _vp, _i, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp,
+                               _vp, _sz, _vp], _i),
     "rr_rank_workspace_bytes": ([_ll, _i], _sz),
     "rr_rank_full": ([_vp, _ll, _vp, _i, _i, _vp, _vp, _sz, _vp], _i),
     "rr_set_tuning": ([_i, _i], _i),

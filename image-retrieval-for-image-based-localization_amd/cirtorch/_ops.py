@@ -858,3 +858,148 @@ def detect_keypoints(x, num, kind="harris", k=0.04, ks=5, min_score=0.0, border=
                                         E.ptr(scores), E.ptr(count), E.ptr(smap), E.ptr(ws), ws.numel(), _st()),
             "rr_detect_keypoints")
     return (kpts, scores, count, smap) if return_response else (kpts, scores, count)
+
+
+# ---------------------------------------------------------------- keypoint description
+PATCH_SIZES = (8, 64)
+
+
+def sift_geometry(patch_size, num_spatial_bins):
+    """(ksize, stride, pad) of get_sift_bin_ksize_stride_pad, or None when the pair is incompatible"""
+    ksize = 2 * int(patch_size / (num_spatial_bins + 1))
+    stride = patch_size // num_spatial_bins
+    pad = ksize // 4
+    if ksize < 1 or stride < 1 or (patch_size + 2 * pad - (ksize - 1) - 1) // stride + 1 != num_spatial_bins:
+        return None
+    return ksize, stride, pad
+
+
+def _no_grad(what, *tensors):
+    for t in tensors:
+        if t is not None and t.requires_grad:
+            raise RuntimeError("%s: gradients are not supported (the kernels have no backward pass); detach the input" % what)
+
+
+def _describe_image(x, what):
+    E.require_gpu(x)
+    if x.dim() != 4:
+        raise ValueError("%s: expected [B, C, H, W], got %s" % (what, tuple(x.shape)))
+    if x.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("%s: images are float32 or uint8, got %s" % (what, x.dtype))
+    return x.contiguous()
+
+
+def _patch_size(ps, what):
+    if not PATCH_SIZES[0] <= int(ps) <= PATCH_SIZES[1]:
+        raise ValueError("%s: patch size %r outside [8, 64]" % (what, ps))
+    return int(ps)
+
+
+def _patches(patches, what):
+    E.require_gpu(patches)
+    _no_grad(what, patches)
+    if patches.dim() < 2 or not patches.is_floating_point() or patches.shape[-1] != patches.shape[-2]:
+        raise RuntimeError("%s: floating-point square patches [..., PS, PS], got %s %s" % (what, patches.dtype, tuple(patches.shape)))
+    return patches.float().contiguous()   # the kernels read float32 (the reference also takes float64)
+
+
+def extract_patches(x, lafs, ps=32, gray=False):
+    """rr_extract_patches: x [B, C, H, W] float32 or uint8, lafs [B, N, 2, 3] float32 pixels ->
+    float32 [B, N, C, ps, ps] ([B, N, 1, ps, ps] with gray=True, C == 3).  No synchronisation."""
+    x = _describe_image(x, "extract_patches")
+    E.require_gpu(lafs)
+    _no_grad("extract_patches", x, lafs)
+    n, c, h, w = x.shape
+    if lafs.dim() != 4 or lafs.shape[0] != n or tuple(lafs.shape[2:]) != (2, 3):
+        raise ValueError("extract_patches: lafs must be [%d, N, 2, 3], got %s" % (n, tuple(lafs.shape)))
+    if gray and c != 3:
+        raise ValueError("extract_patches: gray needs C == 3, got %d" % c)
+    ps = _patch_size(ps, "extract_patches")
+    lafs = lafs.float().contiguous()
+    npts = lafs.shape[1]
+    out = torch.empty((n, npts, 1 if gray else c, ps, ps), dtype=torch.float32, device=x.device)
+    E.check(E.lib().rr_extract_patches(E.ptr(x), n, c, h, w, int(x.dtype == torch.uint8), int(bool(gray)), E.ptr(lafs),
+                                       npts, ps, E.ptr(out), _st()), "rr_extract_patches")
+    return out
+
+
+def patch_orientation(patches, num_ang_bins=36):
+    """rr_patch_orientation: float32 patches [..., ps, ps] -> angles [...] in radians.  No synchronisation."""
+    patches = _patches(patches, "patch_orientation")
+    ps = _patch_size(patches.shape[-1], "patch_orientation")
+    if not 1 <= int(num_ang_bins) <= 64:
+        raise ValueError("patch_orientation: num_ang_bins = %r outside [1, 64]" % (num_ang_bins,))
+    lead = patches.shape[:-2]
+    out = torch.empty(lead, dtype=torch.float32, device=patches.device)
+    E.check(E.lib().rr_patch_orientation(E.ptr(patches), out.numel(), ps, int(num_ang_bins), E.ptr(out), _st()),
+            "rr_patch_orientation")
+    return out
+
+
+def _sift_args(ps, num_ang_bins, num_spatial_bins, what):
+    if not 1 <= int(num_ang_bins) <= 16:
+        raise ValueError("%s: num_ang_bins = %r outside [1, 16]" % (what, num_ang_bins))
+    if not 1 <= int(num_spatial_bins) <= 8:
+        raise ValueError("%s: num_spatial_bins = %r outside [1, 8]" % (what, num_spatial_bins))
+    if sift_geometry(ps, int(num_spatial_bins)) is None:
+        raise ValueError("%s: patch size %d is incompatible with %d spatial bins" % (what, ps, num_spatial_bins))
+    return int(num_ang_bins), int(num_spatial_bins)
+
+
+def sift_describe(patches, num_ang_bins=8, num_spatial_bins=4, rootsift=True, clipval=0.2):
+    """rr_sift_describe: float32 patches [..., ps, ps] -> descriptors [..., num_ang_bins * ns^2].
+    No synchronisation."""
+    patches = _patches(patches, "sift_describe")
+    ps = _patch_size(patches.shape[-1], "sift_describe")
+    nb, ns = _sift_args(ps, num_ang_bins, num_spatial_bins, "sift_describe")
+    lead = tuple(patches.shape[:-2])
+    out = torch.empty(lead + (nb * ns * ns,), dtype=torch.float32, device=patches.device)
+    B = patches.numel() // (ps * ps)
+    E.check(E.lib().rr_sift_describe(E.ptr(patches), B, ps, nb, ns, int(bool(rootsift)), float(clipval), E.ptr(out), _st()),
+            "rr_sift_describe")
+    return out
+
+
+def describe_keypoints(x, kpts=None, count=None, scale=12.0, lafs=None, orient=False, orient_bins=36, ps=32, num_ang_bins=8,
+                       num_spatial_bins=4, rootsift=True, clipval=0.2, return_lafs=False):
+    """rr_describe_keypoints: x [B, 1|3, H, W] float32 or uint8, kpts [B, N, 2] pixel (x, y) (or
+    lafs [B, N, 2, 3]), count int32 [B] or None -> (desc float32 [B, N, dim], angles float32 [B, N])
+    and, with return_lafs, the described frames [B, N, 2, 3].  No synchronisation."""
+    x = _describe_image(x, "describe_keypoints")
+    n, c, h, w = x.shape
+    if c not in (1, 3):
+        raise ValueError("describe_keypoints: images are [B, 1, H, W] or [B, 3, H, W], got C = %d" % c)
+    E.require_gpu(kpts, count, lafs)
+    _no_grad("describe_keypoints", x, kpts, lafs)
+    if lafs is not None:
+        if lafs.dim() != 4 or lafs.shape[0] != n or tuple(lafs.shape[2:]) != (2, 3):
+            raise ValueError("describe_keypoints: lafs must be [%d, N, 2, 3], got %s" % (n, tuple(lafs.shape)))
+        lafs = lafs.float().contiguous()
+        npts = lafs.shape[1]
+        kpts = None
+    else:
+        if kpts is None or kpts.dim() != 3 or kpts.shape[0] != n or kpts.shape[2] != 2:
+            raise ValueError("describe_keypoints: kpts must be [%d, N, 2], got %s"
+                             % (n, None if kpts is None else tuple(kpts.shape)))
+        kpts = kpts.float().contiguous()
+        npts = kpts.shape[1]
+        if not (float(scale) > 0.0 and float(scale) != float("inf")):
+            raise ValueError("describe_keypoints: scale must be positive and finite, got %r" % (scale,))
+    if count is not None:
+        if count.dim() != 1 or count.shape[0] != n or count.dtype != torch.int32:
+            raise ValueError("describe_keypoints: count must be int32 [%d], got %s %s" % (n, count.dtype, tuple(count.shape)))
+        count = count.contiguous()
+    ps = _patch_size(ps, "describe_keypoints")
+    nb, ns = _sift_args(ps, num_ang_bins, num_spatial_bins, "describe_keypoints")
+    if orient and not 1 <= int(orient_bins) <= 64:
+        raise ValueError("describe_keypoints: orientation bins = %r outside [1, 64]" % (orient_bins,))
+    dev = x.device
+    desc = torch.empty((n, npts, nb * ns * ns), dtype=torch.float32, device=dev)
+    angles = torch.empty((n, npts), dtype=torch.float32, device=dev)
+    lafs_out = torch.empty((n, npts, 2, 3), dtype=torch.float32, device=dev) if return_lafs else None
+    ws = torch.empty(int(E.lib().rr_describe_workspace_bytes(n, npts, ps, nb, ns)), dtype=torch.uint8, device=dev)
+    E.check(E.lib().rr_describe_keypoints(E.ptr(x), n, c, h, w, int(x.dtype == torch.uint8), E.ptr(kpts), E.ptr(count), npts,
+                                          float(scale), E.ptr(lafs), int(bool(orient)), int(orient_bins), ps, nb, ns,
+                                          int(bool(rootsift)), float(clipval), E.ptr(desc), E.ptr(angles), E.ptr(lafs_out),
+                                          E.ptr(ws), ws.numel(), _st()), "rr_describe_keypoints")
+    return (desc, angles, lafs_out) if return_lafs else (desc, angles)

@@ -1,9 +1,28 @@
 """Pixel <-> normalised coordinates (``cirtorch/geometry/conversions.py:456-492``): the step between
 ``detect_keypoints`` (pixels) and ``localHead.forward`` (grid coordinates in [-1, 1]), plain
-elementwise torch on whatever device the coordinates live on.
+elementwise torch on whatever device the coordinates live on; and the reference's ``pi``, ``rad2deg``
+and ``deg2rad`` (``:29-44``), which the LAF helpers use.
 """
 
 import torch
+
+# a float32 tensor, as the reference's (``conversions.py:29``): in a float64 computation it is still
+# the float32 value of pi, which the describe kernels reproduce
+pi = torch.tensor(3.14159265358979323846)
+
+
+def rad2deg(tensor):
+    """
+        Radians -> degrees.
+    """
+    return 180. * tensor / pi.to(tensor.device).type(tensor.dtype)
+
+
+def deg2rad(tensor):
+    """
+        Degrees -> radians.
+    """
+    return tensor * pi.to(tensor.device).type(tensor.dtype) / 180.
 
 
 def _factor(pixel_coordinates, height, width, eps):

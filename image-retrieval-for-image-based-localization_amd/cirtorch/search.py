@@ -14,6 +14,8 @@
   (nn / mnn / snn / smnn of ``cirtorch/features/matching.py``), no host sync.
 * ``detect_keypoints``      -> the best N corners / blobs of every image of a batch (response,
   non-maxima suppression and top-N selection on the device), no host sync.
+* ``describe_keypoints``    -> SIFT / RootSIFT descriptors of those keypoints straight from the image
+  (patch, optional dominant orientation and descriptor in one kernel), no host sync.
 
 Layouts: the reference keeps descriptors as D x N columns; the engine reads
 row-major [N][D].  ``vecs.t()`` of a D x N column matrix produced by
@@ -410,6 +412,35 @@ def detect_keypoints(images, num_features=2048, response="harris", k=0.04, nms=5
         nms = nms[0]
     return _ops.detect_keypoints(images, int(num_features), response, float(k), nms, float(min_score), int(border),
                                  sigmas, return_response)
+
+
+def describe_keypoints(images, kpts, count=None, scale=12.0, lafs=None, orientation=False, patch_size=32, num_ang_bins=8,
+                       num_spatial_bins=4, rootsift=True, clipval=0.2):
+    """SIFT descriptors of the keypoints of a batch of images in one call (rr_describe_keypoints):
+    the patch of ``extract_patches_simple`` (``cirtorch/features/laf.py``), optionally the dominant
+    gradient orientation of ``LAFOrienter`` (``cirtorch/features/orientation.py``, 36 bins) and the
+    ``SIFTDescriptor`` of ``cirtorch/features/siftdesc.py`` -- the device-side replacement of the
+    descriptor half of ``generate_kpts(..., 'sift')``.  It takes what ``detect_keypoints`` returns.
+
+    images  [B, 1|3, H, W], float32 in [0, 1] or uint8 (a pixel is v / 255); three channels are
+            reduced by 0.299 r + 0.587 g + 0.114 b
+    kpts    float32 [B, N, 2] pixel (x, y); count int32 [B] or None.  The frame of a keypoint is
+            [[scale, 0, x], [0, scale, y]]: the patch covers 2 * scale pixels a side.  lafs
+            [B, N, 2, 3] (pixels), when given, are the frames instead (kpts is then ignored; with
+            orientation=True they are made upright first).
+    ->      desc float32 [B, N, num_ang_bins * num_spatial_bins ** 2] (L2-normalised; RootSIFT by
+            default), angles float32 [B, N] in radians (0 without orientation).  Slots at or past
+            count and slots whose keypoint is (-1, -1) hold zeros.
+
+    Patches are sampled from the image itself (pyramid level 0; the reference's pyramid agrees
+    while 2 * scale / patch_size < sqrt(2)).  float64 arithmetic rounded once: bit-identical run to
+    run and independent of the batch.  No patch is written to memory and nothing waits for the
+    host: graph-capturable for fixed shapes.  No gradients."""
+    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] not in (1, 3):
+        raise ValueError("describe_keypoints: images are [B, 1, H, W] or [B, 3, H, W], got %s"
+                         % (tuple(images.shape) if torch.is_tensor(images) else type(images),))
+    return _ops.describe_keypoints(images, kpts, count, float(scale), lafs, bool(orientation), 36, int(patch_size),
+                                   int(num_ang_bins), int(num_spatial_bins), bool(rootsift), float(clipval))
 
 
 def _match_rows(x):

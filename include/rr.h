@@ -526,6 +526,96 @@ int rr_detect_keypoints(const void* x, int n, int c, int h, int w, int u8, int k
                         int num, float min_score, int border, float* kpts, float* scores, int* count, float* score_map,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* Keypoint description (rr_describe.hip): local-affine-frame (LAF) patches, the dominant gradient
+ * orientation of a patch, the SIFT descriptor of a patch, and the three fused per keypoint.  Common
+ * to the four entries: all arithmetic is float64 in one fixed order per output and rounded once to
+ * float32, no atomic touches a floating-point value, a result depends on its own patch only (not on
+ * the batch, the slot, the launch or the run), argument errors are returned before anything is
+ * enqueued, and nothing waits for the host (graph-capturable).  pi below is the float32 value
+ * 3.14159274... that the reference's pi tensor (cirtorch/geometry/conversions.py:29) holds, also in
+ * its float64 run.  8 <= ps <= 64.  One block of 256 threads works on one patch or keypoint slot and
+ * a grid holds fewer than 2^32 threads, so a call takes at most 2^24 - 1 patches (extract: n npts
+ * channels) or slots; more is an argument error, split the batch.
+ *
+ * rr_extract_patches replaces extract_patches_simple and generate_patch_grid_from_normalized_LAF
+ * (cirtorch/features/laf.py:260-308: normalize_laf, denormalize_laf, F.affine_grid, F.grid_sample
+ * with bilinear, border, align_corners=False) without the normalise / denormalise round trip.
+ * x [n][c][h][w] float32, or uint8 with u8 = 1 (a pixel is float32(v) / 255.0f, as in rr_response);
+ * gray = 1: c must be 3 and a pixel is (0.299 r + 0.587 g) + 0.114 b, one output channel.
+ * lafs [n][npts][2][3] float32 in pixels.  out [n][npts][c or 1][ps][ps] float32.  For patch row i,
+ * column j and frame [[a00, a01, a02], [a10, a11, a12]]:
+ *   u = (2 j + 1) / ps - 1,  v = (2 i + 1) / ps - 1
+ *   sx = ((a00 u + a01 v) + a02) - 0.5 clamped to [0, w - 1],  sy likewise with row 1 and h
+ *   x0 = floor(sx), x1 = min(x0 + 1, w - 1), fx = sx - x0 (y likewise)
+ *   value = ((p00 (1-fx)(1-fy) + p01 fx (1-fy)) + p10 (1-fx) fy) + p11 fx fy
+ * A frame with a non-finite entry gives a zero patch (the reference is undefined there).
+ * Errors: null pointers, c < 1, h or w < 1, a bad gray, ps, npts < 0, more than 2^31 image pixels,
+ * more than 2^24 - 1 patches.  n npts == 0 returns RR_OK. */
+int rr_extract_patches(const void* x, int n, int c, int h, int w, int u8, int gray, const float* lafs, int npts, int ps,
+                       float* out, void* stream);
+/* rr_patch_orientation replaces PatchDominantGradientOrientation.forward
+ * (cirtorch/features/orientation.py:56-105).  patches [B][ps][ps] float32, 1 <= num_ang_bins <= 64,
+ * angle [B] float32 in radians.  Per pixel, on clamped patch coordinates, dx and dy are the Sobel
+ * pair / 8 of rr_response,
+ *   mag = sqrt((dx^2 + dy^2) + 1e-8),  ori = atan2(dy, dx + 1e-8) + 2 pi
+ *   o = nb (ori + pi) / (2 pi),  b0 = floor(o),  w1 = o - b0
+ * bin b0 mod nb takes (1 - w1) mag and bin (b0 + 1) mod nb takes w1 mag; a bin is the MEAN over the
+ * patch.  No Gaussian weight: the reference builds one and never applies it.  The histogram is
+ * smoothed circularly with the float32 values of [0.33, 0.34, 0.33]; idx is the argmax (ties to the
+ * lower index) and angle = -((2 pi idx) / nb - pi).
+ * Errors: null pointers, a bad ps or num_ang_bins, B outside [0, 2^24).  B == 0 returns RR_OK. */
+int rr_patch_orientation(const float* patches, long long B, int ps, int num_ang_bins, float* angle, void* stream);
+/* rr_sift_describe replaces SIFTDescriptor.forward (cirtorch/features/siftdesc.py:78-129).
+ * patches [B][ps][ps] float32, 1 <= num_ang_bins <= 16, 1 <= num_spatial_bins <= 8,
+ * out [B][num_ang_bins ns^2] float32.  (ps, ns) must pass get_sift_bin_ksize_stride_pad
+ * (siftdesc.py:21-37): ksize = 2 int(ps / (ns + 1)), stride = ps / ns, pad = ksize / 4 and
+ * (ps + 2 pad - ksize) / stride + 1 == ns, else RR_EINVAL.  Per pixel, on clamped patch coordinates:
+ *   gx = (p(y, x+1) - p(y, x-1)) / 2,  gy = (p(y+1, x) - p(y-1, x)) / 2
+ *   mag = sqrt((gx^2 + gy^2) + 1e-10) G(y, x),  ori = atan2(gy, gx + 1e-10) + 2 pi
+ *   o = (nb ori) / (2 pi),  b0 = floor(o),  w1 = o - b0
+ * bin b0 mod nb takes (1 - w1) mag, bin (b0 + 1) mod nb takes w1 mag.  G is float32-valued, as in
+ * the reference: G(y, x) = g(y) g(x) multiplied in float32, g the 1-D Gaussian of sigma =
+ * ps / sqrt 2 at x - ps / 2 (+ 0.5 for even ps), normalised to sum 1 (computed in float64, each
+ * weight rounded to float32; the reference's float32 exponentials differ from that in the last
+ * place).  Each angular plane is pooled by the ksize x ksize kernel with the float32 values
+ * (xc(ky) xc(kx)) / (ksize / 2)^2, xc(k) = ksize / 2 - |k + 0.5 - ksize / 2|, at stride and pad with
+ * zeros outside the patch; out index a ns^2 + cy ns + cx.  Then v / max(|v|_2, 1e-12), clamp to
+ * [0, clipval], v / max(|v|_2, 1e-12) and, with rootsift, sqrt(v / max(|v|_1, 1e-12) + 1e-10).
+ * Errors: null pointers, bad sizes or bins, an incompatible (ps, ns), a non-finite clipval, B outside
+ * [0, 2^24).  B == 0 returns RR_OK. */
+int rr_sift_describe(const float* patches, long long B, int ps, int num_ang_bins, int num_spatial_bins, int rootsift,
+                     double clipval, float* out, void* stream);
+/* rr_describe_keypoints: image -> descriptors in one kernel, one block per keypoint, the patch in
+ * LDS: no patch, gradient, histogram or angular plane exists in memory.  It replaces the
+ * descriptor half of generate_kpts(..., 'sift') (cirtorch/datasets/localFeatures/utils.py:56-99),
+ * i.e. LAFOrienter.forward (orientation.py:122-150) followed by extract_patches_simple and
+ * SIFTDescriptor.forward.
+ * x [n][c][h][w] float32 or uint8, c = 1, or c = 3 reduced to gray.  The frame of slot (i, k):
+ * lafs [n][npts][2][3] when lafs is not NULL, else [[scale, 0, x], [0, scale, y]] with (x, y) =
+ * kpts [n][npts][2], which is what rr_select_keypoints writes.  count: NULL or int32 [n]; slots at
+ * or past count[i] and slots whose centre is (-1, -1) get an all-zero descriptor, angle 0 and a zero
+ * frame.  orient = 1: the upright frame U is make_upright (laf.py:112-134) in float64, rounded to
+ * float32 (the frame itself when it comes from scale); the patch of U gives theta by
+ * rr_patch_orientation with orient_bins bins, and the frame becomes U . [[cos theta, sin theta],
+ * [-sin theta, cos theta]] -- the float32 U that was sampled, turned in float64 and rounded once to
+ * float32 -- before the patch is sampled again.  orient = 0 samples the
+ * frame as given.  desc [n][npts][num_ang_bins ns^2]; angles (NULL or [n][npts]) and lafs_out (NULL
+ * or [n][npts][2][3]) receive theta and the frame that was described.
+ * The result is bit-identical to rr_extract_patches (gray = 1 for c = 3) on lafs_out followed by
+ * rr_sift_describe, and theta to rr_patch_orientation on the patches of the upright frames.
+ * Patches are always sampled from the image itself (pyramid level 0 of
+ * extract_patches_from_pyramid, which LAFOrienter calls: the two agree while 2 scale / ps < sqrt 2).
+ * The workspace (rr_describe_workspace_bytes) is a formality of 256 bytes today.
+ * Errors: those of the entries above, c not 1 or 3, orient not 0 / 1, a scale that is not positive
+ * and finite when lafs is NULL, kpts and lafs both NULL, more than 2^24 - 1 slots, a short workspace
+ * (RR_ENOSPACE).
+ * n npts == 0 returns RR_OK. */
+size_t rr_describe_workspace_bytes(int n, int npts, int ps, int num_ang_bins, int num_spatial_bins);
+int rr_describe_keypoints(const void* x, int n, int c, int h, int w, int u8, const float* kpts, const int* count, int npts,
+                          double scale, const float* lafs, int orient, int orient_bins, int ps, int num_ang_bins,
+                          int num_spatial_bins, int rootsift, double clipval, float* desc, float* angles, float* lafs_out,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* Full ranking for any database size: out_idx[q][r] = the r-th database row of
  * query q by (float64 score desc, index asc) — np.argsort(-np.dot(vecs.T, qvecs),
  * axis=0) of scripts/test.py:247-248 as [nq][n] (rr_knn_topk ranks k <= 8192).
