@@ -23,7 +23,7 @@ RR_POOL_GEM, RR_POOL_MAC, RR_POOL_SPOC = 0, 1, 2
 RR_CONV_AFFINE, RR_CONV_RESIDUAL, RR_CONV_PERM32 = 1, 2, 4
 RR_NHWC, RR_NCHW = 0, 1
 RR_MATCH_NN, RR_MATCH_MNN, RR_MATCH_SNN, RR_MATCH_SMNN = 0, 1, 2, 3
-RR_RESP_HARRIS, RR_RESP_GFTT, RR_RESP_HESSIAN = 0, 1, 2
+RR_RESP_HARRIS, RR_RESP_GFTT, RR_RESP_HESSIAN, RR_RESP_DOG = 0, 1, 2, 3
 
 _DTYPE_CODE = {torch.float32: RR_F32, torch.bfloat16: RR_BF16, torch.float16: RR_F16,
                torch.int8: RR_I8}  # RR_I8: kNN screening only
@@ -100,6 +100,14 @@ _SIGS = {
     "rr_select_keypoints": ([_vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp], _i),
     "rr_detect_keypoints": ([_vp, _i, _i, _i, _i, _i, _i, _d, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz,
                              _vp], _i),
+    "rr_gaussian_blur": ([_vp, _ll, _i, _i, _i, _d, _vp, _vp], _i),
+    "rr_scale_pyramid_bytes": ([_i, _i, _i, _i, _i, _d, _i, ctypes.POINTER(_sz), ctypes.POINTER(_sz)], _i),
+    "rr_scale_pyramid": ([_vp, _i, _i, _i, _i, _i, _i, _d, _i, _vp, _sz, _vp, _sz, _vp], _i),
+    "rr_dog_response": ([_vp, _i, _i, _i, _i, _vp, _vp], _i),
+    "rr_scale_space_extrema": ([_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "rr_scale_space_select": ([_vp, _i, _i, _i, _i, _d, _i, _i, _d, _i, _vp, _vp, _vp, _vp, _sz, _vp], _i),
+    "rr_detect_scale_space_workspace_bytes": ([_i, _i, _i, _i, _i, _d, _i], _sz),
+    "rr_detect_scale_space": ([_vp, _i, _i, _i, _i, _i, _i, _d, _i, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp, _sz, _vp], _i),
     "rr_describe_workspace_bytes": ([_i, _i, _i, _i, _i], _sz),
     "rr_extract_patches": ([_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp], _i),
     "rr_patch_orientation": ([_vp, _ll, _i, _i, _vp, _vp], _i),

@@ -860,6 +860,174 @@ def detect_keypoints(x, num, kind="harris", k=0.04, ks=5, min_score=0.0, border=
     return (kpts, scores, count, smap) if return_response else (kpts, scores, count)
 
 
+# ---------------------------------------------------------------- scale-space detection
+SS_RESPONSES = dict(RESPONSES, dog=E.RR_RESP_DOG)
+
+
+def pyramid_plan(n, h, w, levels=3, sigma=1.6, min_size=15):
+    """The host arithmetic of ScalePyramid (the rule of rr_scale_pyramid in include/rr.h): a list of
+    octaves, each a dict with h, w, off (floats from the start of the pyramid buffer), sigmas (one
+    per level) and blurs ((ksize, sigma) per level; level 0 of octave 0 holds the first blur or None)."""
+    import math
+    L = levels + 3
+    step = 2 ** (1. / float(levels))
+    cur = 0.5
+    first = None
+    if sigma > cur:
+        s0 = max(math.sqrt(sigma ** 2 - cur ** 2), 0.01)
+        k0 = int(2.0 * 4.0 * s0 + 1.0)
+        first = (k0 + 1 if k0 % 2 == 0 else k0, s0)
+        cur = sigma
+    octs, off = [], 0
+    while True:
+        o = dict(h=h, w=w, off=off, sigmas=[cur], blurs=[first if not octs else None])
+        for _ in range(1, L):
+            s = cur * math.sqrt(step ** 2 - 1.0)
+            ks = int(2.0 * 4.0 * s + 1.0)
+            if ks % 2 == 0:
+                ks += 1
+            ks = min(ks, min(h, w))
+            if ks % 2 == 0:
+                ks += 1
+            cur *= step
+            o["sigmas"].append(cur)
+            o["blurs"].append((ks, s))
+        octs.append(o)
+        off += (n * L * h * w + 63) // 64 * 64
+        h, w = h // 2, w // 2
+        cur = sigma
+        if min(h, w) <= min_size:
+            break
+    return octs
+
+
+def _pyr_input(x, what):
+    E.require_gpu(x)
+    if x.dim() != 4 or x.shape[1] not in (1, 3):
+        raise ValueError("%s: images are [B, 1, H, W] or [B, 3, H, W], got %s" % (what, tuple(x.shape)))
+    if x.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("%s: images are float32 or uint8, got %s" % (what, x.dtype))
+    return x.contiguous()
+
+
+def _pyr_views(buf, n, L, octs):
+    return [buf[o["off"]:o["off"] + n * L * o["h"] * o["w"]].view(n, 1, L, o["h"], o["w"]) for o in octs]
+
+
+def gaussian_blur(x, ksize, sigma):
+    """rr_gaussian_blur: float32 planes [..., H, W], reflect borders -> the same shape.  No synchronisation."""
+    E.require_gpu(x)
+    if x.dim() < 2 or x.dtype != torch.float32:
+        raise RuntimeError("gaussian_blur: float32 planes [..., H, W], got %s %s" % (x.dtype, tuple(x.shape)))
+    x = x.contiguous()
+    h, w = x.shape[-2:]
+    planes = x.numel() // (h * w) if h * w else 0
+    out = torch.empty_like(x)
+    E.check(E.lib().rr_gaussian_blur(E.ptr(x), planes, h, w, int(ksize), float(sigma), E.ptr(out), _st()), "rr_gaussian_blur")
+    return out
+
+
+def scale_pyramid(x, levels=3, sigma=1.6, min_size=15):
+    """rr_scale_pyramid: x [B, 1|3, H, W] float32 or uint8 -> (views [B, 1, L, h_o, w_o] of one float32
+    buffer, one per octave; the plan of pyramid_plan).  No synchronisation."""
+    x = _pyr_input(x, "scale_pyramid")
+    n, c, h, w = x.shape
+    ob, wb = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    args = (int(levels), float(sigma), int(min_size))
+    E.check(E.lib().rr_scale_pyramid_bytes(n, c, h, w, *args, ctypes.byref(ob), ctypes.byref(wb)), "rr_scale_pyramid_bytes")
+    out = torch.empty(ob.value // 4, dtype=torch.float32, device=x.device)
+    ws = torch.empty(wb.value, dtype=torch.uint8, device=x.device)
+    E.check(E.lib().rr_scale_pyramid(E.ptr(x), n, c, h, w, int(x.dtype == torch.uint8), *args, E.ptr(out), ob.value,
+                                     E.ptr(ws), ws.numel(), _st()), "rr_scale_pyramid")
+    octs = pyramid_plan(n, h, w, *args)
+    return _pyr_views(out, n, int(levels) + 3, octs), octs
+
+
+def dog_response(levels):
+    """rr_dog_response: float32 [B, L, H, W] -> [B, L - 1, H, W].  No synchronisation."""
+    E.require_gpu(levels)
+    if levels.dim() != 4 or levels.dtype != torch.float32:
+        raise RuntimeError("dog_response: float32 levels [B, L, H, W], got %s %s" % (levels.dtype, tuple(levels.shape)))
+    levels = levels.contiguous()
+    n, L, h, w = levels.shape
+    if L < 2:
+        raise ValueError("dog_response: at least two levels, got %d" % L)
+    out = torch.empty((n, L - 1, h, w), dtype=torch.float32, device=levels.device)
+    E.check(E.lib().rr_dog_response(E.ptr(levels), n, L, h, w, E.ptr(out), _st()), "rr_dog_response")
+    return out
+
+
+def scale_space_extrema(x, minima=False):
+    """rr_scale_space_extrema: a float32 volume [B, D, H, W] -> (mask uint8 [B, D, H, W]: 1 maximum,
+    2 minimum; offsets float32 [B, 3, D, H, W] in the order (level, x, y); values float32 [B, D, H, W]).
+    No synchronisation."""
+    E.require_gpu(x)
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise RuntimeError("scale_space_extrema: a float32 volume [B, D, H, W], got %s %s" % (x.dtype, tuple(x.shape)))
+    x = x.contiguous()
+    n, D, h, w = x.shape
+    mask = torch.empty((n, D, h, w), dtype=torch.uint8, device=x.device)
+    offs = torch.empty((n, 3, D, h, w), dtype=torch.float32, device=x.device)
+    vals = torch.empty((n, D, h, w), dtype=torch.float32, device=x.device)
+    E.check(E.lib().rr_scale_space_extrema(E.ptr(x), n, D, h, w, int(bool(minima)), E.ptr(mask), E.ptr(offs), E.ptr(vals),
+                                           _st()), "rr_scale_space_extrema")
+    return mask, offs, vals
+
+
+def _ss_args(num, mr_size):
+    if not 1 <= int(num) <= 8192:
+        raise ValueError("keypoints: num_features = %r outside [1, 8192]" % (num,))
+    if not float(mr_size) > 0:
+        raise ValueError("keypoints: mr_size = %r must be positive" % (mr_size,))
+
+
+def _ss_outputs(n, num, dev):
+    return (torch.empty((n, num, 2, 3), dtype=torch.float32, device=dev), torch.empty((n, num), dtype=torch.float32, device=dev),
+            torch.empty(n, dtype=torch.int32, device=dev))
+
+
+def scale_space_select(resp, n, h, w, num, levels=3, sigma=1.6, min_size=15, minima=False, mr_size=6.0):
+    """rr_scale_space_select: resp, a float32 buffer in the pyramid's layout for n images of h x w ->
+    (lafs float32 [n, num, 2, 3], scores [n, num], count int32 [n]).  No synchronisation."""
+    E.require_gpu(resp)
+    _ss_args(num, mr_size)
+    args = (int(levels), float(sigma), int(min_size))
+    need = pyramid_plan(n, h, w, *args)[-1]
+    if resp.dtype != torch.float32 or resp.dim() != 1 or resp.numel() < need["off"] + n * (args[0] + 3) * need["h"] * need["w"]:
+        raise RuntimeError("scale_space_select: resp must be the flat float32 buffer of the pyramid's layout")
+    lafs, scores, count = _ss_outputs(n, int(num), resp.device)
+    ws = torch.empty(int(E.lib().rr_detect_scale_space_workspace_bytes(n, 1, h, w, *args)), dtype=torch.uint8, device=resp.device)
+    E.check(E.lib().rr_scale_space_select(E.ptr(resp), n, h, w, *args, int(bool(minima)), float(mr_size), int(num), E.ptr(lafs),
+                                          E.ptr(scores), E.ptr(count), E.ptr(ws), ws.numel(), _st()), "rr_scale_space_select")
+    return lafs, scores, count
+
+
+def detect_scale_space(x, num, kind="hessian", levels=3, sigma=1.6, min_size=15, mr_size=6.0, minima=False, k=0.04,
+                       return_pyramid=False):
+    """rr_detect_scale_space: x [B, 1|3, H, W] float32 or uint8 -> (lafs float32 [B, num, 2, 3] in image
+    pixels, scores [B, num], count int32 [B]); with return_pyramid also the views of the pyramid the
+    call left at the start of its workspace.  No synchronisation."""
+    if kind not in SS_RESPONSES:
+        raise ValueError("response %r (one of harris, gftt, hessian, dog)" % (kind,))
+    _ss_args(num, mr_size)
+    x = _pyr_input(x, "detect_scale_space")
+    n, c, h, w = x.shape
+    args = (int(levels), float(sigma), int(min_size))
+    lafs, scores, count = _ss_outputs(n, int(num), x.device)
+    nbytes = int(E.lib().rr_detect_scale_space_workspace_bytes(n, c, h, w, *args))
+    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=x.device)
+    E.check(E.lib().rr_detect_scale_space(E.ptr(x), n, c, h, w, int(x.dtype == torch.uint8), *args, SS_RESPONSES[kind],
+                                          float(k), int(bool(minima)), float(mr_size), int(num), E.ptr(lafs), E.ptr(scores),
+                                          E.ptr(count), E.ptr(ws), nbytes, _st()), "rr_detect_scale_space")
+    if not return_pyramid:
+        return lafs, scores, count
+    pad = (-ws.data_ptr()) % 256
+    octs = pyramid_plan(n, h, w, *args)
+    total = octs[-1]["off"] + n * (args[0] + 3) * octs[-1]["h"] * octs[-1]["w"]
+    buf = ws[pad:pad + 4 * total].view(torch.float32)
+    return lafs, scores, count, _pyr_views(buf, n, args[0] + 3, octs)
+
+
 # ---------------------------------------------------------------- keypoint description
 PATCH_SIZES = (8, 64)
 

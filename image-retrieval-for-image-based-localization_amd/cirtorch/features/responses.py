@@ -7,8 +7,9 @@ full-size planes on the way; here one kernel reads the image once and writes the
 float64 rounded once to float32.  Input ``[B, C, H, W]`` float32 or uint8 (a uint8 pixel counts as
 ``v / 255``) on the GPU, output float32 ``[B, C, H, W]``: every plane is scored on its own.
 
-Only ``grads_mode='sobel'`` exists (``'diff'`` raises NotImplementedError); ``dog_response`` and
-``BlobDoG`` belong to the scale pyramid, which is out of scope.
+Only ``grads_mode='sobel'`` exists (``'diff'`` raises NotImplementedError).  ``dog_response`` and
+``BlobDoG`` (``:106-130``) work on the levels of a scale pyramid, ``[B, C, L, H, W]`` float32 ->
+``[B, C, L - 1, H, W]`` (rr_dog_response).
 """
 
 import torch
@@ -116,3 +117,23 @@ class BlobHessian(nn.Module):
 
     def forward(self, input, sigmas=None):
         return hessian_response(input, self.grads_mode, sigmas)
+
+
+def dog_response(input):
+    """
+        Computes the Difference-of-Gaussian response given the Gaussian 5d input: level l + 1 minus level l
+    """
+    if not len(input.shape) == 5:
+        raise ValueError("Invalid input shape, we expect BxCxDxHxW. Got: {}".format(input.shape))
+    B, C, L, H, W = input.shape
+    return _ops.dog_response(input.reshape(B * C, L, H, W)).view(B, C, L - 1, H, W)
+
+
+class BlobDoG(nn.Module):
+    """
+        nn.Module that calculates Difference-of-Gaussians blobs
+        See :func:`dog_response` for details.
+    """
+
+    def forward(self, input, sigmas=None):
+        return dog_response(input)

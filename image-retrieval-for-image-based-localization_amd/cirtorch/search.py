@@ -414,6 +414,40 @@ def detect_keypoints(images, num_features=2048, response="harris", k=0.04, nms=5
                                  sigmas, return_response)
 
 
+def detect_keypoints_scale_space(images, num_features=2048, response="hessian", levels=3, sigma=1.6, min_size=15, mr_size=6.0,
+                                 minima=None, k=0.04):
+    """Scale-covariant keypoints of a batch of images in one call (rr_detect_scale_space): the
+    ``ScalePyramid`` of ``cirtorch/geometry/transform/pyramid.py``, the Hessian, Harris, Shi-Tomasi
+    ("gftt") or difference-of-Gaussians ("dog") response of every level, the strict 3 x 3 x 3 extrema
+    and quadratic refinement of ``ConvQuadInterp3d``, and the frames and top-N selection of
+    ``ScaleSpaceDetector.detect`` (``cirtorch/features/scale_space_detector.py``).
+
+    images  [B, 1|3, H, W], float32 in [0, 1] or uint8 (a pixel is v / 255); three channels are
+            reduced by 0.299 r + 0.587 g + 0.114 b
+    ->      lafs float32 [B, N, 2, 3] in image pixels, [[s, 0, x], [0, s, y]] with
+            s = mr_size * sigma of the keypoint -- what ``describe_keypoints(images, None, lafs=lafs)``
+            takes, and ``get_laf_center(lafs)`` is the (x, y) layout of ``verify_pairs`` --, scores
+            float32 [B, N] (the refined response), count int32 [B]; the slots past count hold a zero
+            frame and score 0.
+
+    The best `num_features` are taken over all octaves by (score desc, octave asc, voxel asc).  With
+    `minima` (default: only for "dog") strict minima count too, scored by -response.  A frame whose
+    circle of radius s leaves its octave is dropped.  float64 arithmetic rounded once: bit-identical
+    run to run and independent of the batch.  No device->host synchronisation: graph-capturable
+    for fixed shapes."""
+    if response not in _ops.SS_RESPONSES:
+        raise ValueError("detect_keypoints_scale_space: response %r (one of harris, gftt, hessian, dog)" % (response,))
+    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] not in (1, 3):
+        raise ValueError("detect_keypoints_scale_space: images are [B, 1, H, W] or [B, 3, H, W], got %s"
+                         % (tuple(images.shape) if torch.is_tensor(images) else type(images),))
+    if images.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("detect_keypoints_scale_space: images are float32 or uint8, got %s" % images.dtype)
+    if minima is None:
+        minima = response == "dog"
+    return _ops.detect_scale_space(images, int(num_features), response, int(levels), float(sigma), int(min_size),
+                                   float(mr_size), bool(minima), float(k))
+
+
 def describe_keypoints(images, kpts, count=None, scale=12.0, lafs=None, orientation=False, patch_size=32, num_ang_bins=8,
                        num_spatial_bins=4, rootsift=True, clipval=0.2):
     """SIFT descriptors of the keypoints of a batch of images in one call (rr_describe_keypoints):

@@ -53,6 +53,7 @@
 // candidates: the lists are sized by that bound and cannot overflow.  A score depends on the pixels
 // of its window only: not on n, the tile, the launch or the run.
 #include "rr_internal.h"
+#include "rr_select.h"
 
 #include <math.h>
 
@@ -64,8 +65,6 @@ constexpr int D_TB = 256;          // threads of k_response
 constexpr int D_T = 32;            // tile side
 constexpr int D_G = D_T + 6;       // gradient slots per side (the blur reaches 3)
 constexpr int D_I = D_T + 8;       // pixel slots per side (the gradient reaches 1 more)
-constexpr int D_SEL_TB = 1024;     // threads of k_select
-constexpr int D_MAXNUM = 8192;     // keypoints per image (64 KiB of keys in LDS)
 constexpr int D_CW = 64, D_CH = 32; // tile of k_candidates
 constexpr int D_CR = 4;            // the largest window radius (ks = 9)
 constexpr long long D_MAXPIX = 1ll << 31;
@@ -273,10 +272,6 @@ __global__ void __launch_bounds__(256) k_nms(const float* __restrict__ x, int h,
     }
 }
 
-__device__ __forceinline__ float key_score(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
-
 __global__ void __launch_bounds__(256) k_reset_counts(int* __restrict__ cnt, int n) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) cnt[i] = 0;
@@ -324,89 +319,14 @@ __global__ void __launch_bounds__(256) k_candidates(const float* __restrict__ x,
         if (base + j < cap) keys[b * cap + base + j] = L.key[j];   // always: cap is the bound on strict maxima
 }
 
-struct SelLds {
-    unsigned long long sel[D_MAXNUM];
-    unsigned int hist[256];
-    unsigned long long prefix;
-    int remaining;
-    int equal;      // keys that share the threshold's bits so far
-    int nsel;
-};
-
 __global__ void __launch_bounds__(D_SEL_TB) k_select(const unsigned long long* __restrict__ keys, const int* __restrict__ cnt,
                                                      long long cap, int w, int num, float* __restrict__ kpts,
                                                      float* __restrict__ scores, int* __restrict__ count) {
     __shared__ SelLds L;
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
-    const unsigned long long* kb = keys + (long long)b * cap;
     const long long m = cnt[b] < cap ? cnt[b] : cap;
-    const int want = (int)(m < num ? m : num);
-    unsigned long long thr = 0ull;
-    if (m > num) {   // the num-th largest key, 8 bits at a time from the top
-        unsigned long long mask = 0ull;
-        if (tid == 0) { L.prefix = 0ull; L.remaining = num; }
-        for (int shift = 56; shift >= 0; shift -= 8) {
-            if (tid < 256) L.hist[tid] = 0u;
-            __syncthreads();
-            const unsigned long long pre = L.prefix;
-            for (long long i0 = tid; i0 < m; i0 += 4 * D_SEL_TB) {   // four loads in flight per thread
-                unsigned long long k[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) k[u] = i0 + u * D_SEL_TB < m ? kb[i0 + u * D_SEL_TB] : 0ull;
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (i0 + u * D_SEL_TB < m && (k[u] & mask) == pre) atomicAdd(&L.hist[(unsigned)(k[u] >> shift) & 255u], 1u);
-            }
-            __syncthreads();
-            // the digit: bin d with fewer than `remaining` keys above it and at least that many from it on
-            int rem = 0;
-            unsigned above = 0u, mine = 0u;
-            if (tid < 256) {
-                rem = L.remaining;
-                for (int j = tid + 1; j < 256; ++j) above += L.hist[j];
-                mine = L.hist[tid];
-            }
-            __syncthreads();   // every thread has read remaining (and prefix)
-            if (tid < 256 && (int)above < rem && (int)(above + mine) >= rem) {
-                L.remaining = rem - (int)above;
-                L.equal = (int)mine;
-                L.prefix = pre | ((unsigned long long)tid << shift);
-            }
-            mask |= 0xffull << shift;
-            __syncthreads();
-            // every key that shares the bits settled so far is wanted: the bits below need no pass
-            if (L.equal == L.remaining) break;
-        }
-        thr = L.prefix;
-    }
-    if (tid == 0) L.nsel = 0;
-    __syncthreads();
-    for (long long i = tid; i < m; i += D_SEL_TB) {
-        const unsigned long long k = kb[i];
-        if (k >= thr) {
-            const int pos = atomicAdd(&L.nsel, 1);
-            if (pos < D_MAXNUM) L.sel[pos] = k;   // always: exactly `want` keys reach thr
-        }
-    }
-    int P = 1;
-    while (P < want) P <<= 1;
-    __syncthreads();
-    for (int i = want + tid; i < P; i += D_SEL_TB) L.sel[i] = 0ull;
-    __syncthreads();
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < P; i += D_SEL_TB) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const unsigned long long a = L.sel[i], c = L.sel[l];
-                    const bool desc = (i & k) == 0;
-                    if (desc ? a < c : a > c) { L.sel[i] = c; L.sel[l] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    const int want = select_sorted(L, keys + (long long)b * cap, m, num);
     float* kp = kpts + (long long)b * num * 2;
     float* sc = scores + (long long)b * num;
     for (int i = tid; i < num; i += D_SEL_TB) {

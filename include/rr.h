@@ -526,6 +526,116 @@ int rr_detect_keypoints(const void* x, int n, int c, int h, int w, int u8, int k
                         int num, float min_score, int border, float* kpts, float* scores, int* count, float* score_map,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* Scale-space keypoint detection (rr_scalespace.hip): image -> Gaussian scale pyramid -> response per
+ * level -> strict 3-D extrema with sub-voxel refinement -> local affine frames (LAFs) -> the best num
+ * frames per image over all octaves.  Replaces ScaleSpaceDetector.detect of
+ * cirtorch/features/scale_space_detector.py:85-161 with ConvQuadInterp3d as its nms module.  Common to
+ * the entries: all arithmetic is float64 in one fixed order per output and every stored value is rounded
+ * once, no atomic touches a floating-point value, a result depends on its own image only (not on the
+ * batch, the launch or the run), argument errors are returned before anything is enqueued and nothing
+ * waits for the host (graph-capturable).
+ *
+ * rr_gaussian_blur: gaussian_blur2d of cirtorch/filters/gaussian.py:8-16 (filter2D of
+ * cirtorch/filters/filter.py:34-77) with border_type 'reflect' on float32 planes x [planes][h][w].
+ * The 1-D taps are the float32-valued weights of get_gaussian_kernel1d(ksize, sigma)
+ * (cirtorch/filters/kernels.py:26-35): e_i = exp(-(i - ksize / 2)^2 / (2 sigma^2)) in float64, their sum
+ * in ascending i, t_i = float32(e_i / sum) -- the rule of rr_sift_describe's window.  The blur is
+ * separable: along x, then along y, taps in ascending offset, on reflected coordinates (-i reads i,
+ * h - 1 + i reads h - 1 - i; the edge sample is not repeated); the x pass is kept in float64 and the
+ * output is rounded once.  ksize is odd, at most 63, and ksize / 2 < min(h, w) (what reflect padding
+ * accepts); sigma > 0.  Errors: those, null pointers, more than 2^31 pixels.  planes == 0 returns RR_OK. */
+int rr_gaussian_blur(const float* x, long long planes, int h, int w, int ksize, double sigma, float* out, void* stream);
+/* rr_scale_pyramid: ScalePyramid.forward of cirtorch/geometry/transform/pyramid.py:30-158 with
+ * double_image = False.  x [n][c][h][w] float32, or uint8 with u8 = 1 (a pixel is float32(v) / 255.0f);
+ * c is 1 or 3, three channels become (0.299 r + 0.587 g) + 0.114 b first.  With L = levels + 3,
+ * step = 2^(1 / levels), ksize(s) = int(8 s + 1) made odd:
+ *   first level   the image blurred by s0 = max(sqrt(sigma^2 - 0.25), 0.01) with ksize(s0) taps when
+ *                 sigma > 0.5 (the level's sigma is then `sigma`), else the image (sigma 0.5);
+ *   level l >= 1  level l - 1 blurred by s = cur sqrt(step^2 - 1), cur the sigma of level l - 1, with
+ *                 min(ksize(s), min(h_o, w_o)) taps made odd again (the reference's cap is part of the
+ *                 rule); its sigma is cur step;
+ *   next octave   its first level is level L - 3 at the even pixels (F.interpolate(scale_factor = 0.5,
+ *                 mode = 'nearest')), size floor(h_o / 2) x floor(w_o / 2), its sigma is `sigma`;
+ *                 octaves stop when the next one's smaller side is <= min_size.
+ * The octave count, the sizes, every sigma and kernel size are host arithmetic from (h, w, levels,
+ * sigma, min_size); nothing is read back.  out holds, octave after octave, [n][1][L][h_o][w_o] float32;
+ * octave o + 1 starts n L h_o w_o floats, rounded up to a multiple of 64, after octave o.  A level is
+ * blurred from the float64 value of the previous level (kept in the workspace), not from its float32
+ * rounding: each float32 level is rounded once.  rr_scale_pyramid_bytes gives the bytes of out and of the
+ * workspace.  1 <= levels <= 8, min_size >= 1, every blur at most 63 taps.
+ * Errors: a bad c, levels, sigma or min_size, h or w too small for the reflect padding of a level
+ * (RR_EINVAL), more than 2^31 pixels in x or in an octave, more than 16 octaves, null pointers, a short
+ * out or workspace (RR_ENOSPACE).  n == 0 returns RR_OK. */
+int rr_scale_pyramid_bytes(int n, int c, int h, int w, int levels, double sigma, int min_size, size_t* out_bytes,
+                           size_t* workspace_bytes);
+int rr_scale_pyramid(const void* x, int n, int c, int h, int w, int u8, int levels, double sigma, int min_size, float* out,
+                     size_t out_bytes, void* workspace, size_t workspace_bytes, void* stream);
+/* dog_response of cirtorch/features/responses.py:106-115: out [n][L - 1][h][w] = levels[:, l + 1] -
+ * levels[:, l] of levels [n][L][h][w] float32.  L >= 2.  n == 0 returns RR_OK. */
+#define RR_RESP_DOG 3
+int rr_dog_response(const float* levels, int n, int L, int h, int w, float* out, void* stream);
+/* rr_scale_space_extrema: nms3d(x, (3, 3, 3)) of cirtorch/features/nms.py:70-108 and conv_quad_interp3d
+ * of cirtorch/geometry/subpix/spatial_soft_argmax.py:348-411 on a volume x [n][D][h][w] float32.
+ * A voxel is a candidate when its value is > 0 and strictly greater than its 26 neighbours at clamped
+ * coordinates, so no voxel on a face of the volume (first and last level included) is kept; NaN is never
+ * kept (the rule of rr_nms2d in three dimensions).  With minima = 1 the same rule on -x gives candidates
+ * too; p below is then -x.  Refinement of a candidate, with p(d, y, x) the volume -- the taps of
+ * spatial_gradient3d(mode = 'diff') of cirtorch/filters/sobel.py:48-78 (replicate border, which no
+ * candidate reaches), whose kernel is flipped along the level axis:
+ *   b = (gx, gy, gs) = (p(x+1) - p(x-1), p(y+1) - p(y-1), p(d-1) - p(d+1)) / 2
+ *   dxx = (p(x-1) + p(x+1)) - 2 p, dyy and dss likewise
+ *   dxy = 0.25 (((p(y-1,x-1) - p(y-1,x+1)) - p(y+1,x-1)) + p(y+1,x+1))
+ *   dys = 0.25 (((p(d-1,y+1) - p(d-1,y-1)) + p(d+1,y-1)) - p(d+1,y+1))
+ *   dxs = 0.25 (((p(d-1,x+1) - p(d-1,x-1)) + p(d+1,x-1)) - p(d+1,x+1))
+ *   H = [[dxx, dxy, dxs], [dxy, dyy, dys], [dxs, dys, dss]],  offset (ox, oy, os) = -H^-1 b
+ * solved in float64 by elimination with partial pivoting; a singular system (a zero pivot) or a
+ * non-finite solution gives a zero offset, and so does any |offset| > 0.7.
+ * value = p + 0.5 ((gx ox + gy oy) + gs os).  The reference's rand * eps on H is left out.
+ * Two deliberate deviations from the reference: it adds the x offset to y and the y offset to x
+ * (create_meshgrid3d orders a voxel (d, x, y) and dx.flip(1) yields (ds, dy, dx)) -- here each offset
+ * belongs to its own axis --, and no strict_maxima_bonus is added to values.
+ * Outputs: mask [n][D][h][w] uint8 (0 none, 1 maximum, 2 minimum), offsets [n][3][D][h][w] float32 in
+ * the order (os, ox, oy) of the reference's coordinates (d, x, y), values [n][D][h][w] float32: the
+ * refined value of a candidate, x elsewhere.
+ * Errors: null pointers, D, h or w < 1, minima not 0 / 1, more than 2^31 voxels.  n == 0 returns RR_OK. */
+int rr_scale_space_extrema(const float* x, int n, int D, int h, int w, int minima, unsigned char* mask, float* offsets,
+                           float* values, void* stream);
+/* Frames and selection (scale_space_detector.py:137-161).  resp has the pyramid's layout (octave after
+ * octave [n][L][h_o][w_o] of (h, w, levels, sigma, min_size)); the volume of an octave is its first
+ * D = L - 1 planes (the reference drops the last level of Hessian, Harris and GFTT; DoG has L - 1).
+ * For each candidate of the rule above with refined coordinates (s, y, x) = (d + os, y + oy, x + ox):
+ *   sig = first_sigma 2^(s / levels), first_sigma the sigma of the octave's first level,
+ *   frame [[a, 0, x], [0, a, y]] in octave pixels, a = mr_size sig.
+ * The frame is dropped unless its centre and the 11 points (x + a sin t_i, y + a cos t_i), t_i the
+ * float32 values of linspace(0, 2 pi, 11) and sin, cos their float32 values -- laf_to_boundary_points(laf,
+ * 12) of laf_is_inside_image, cirtorch/features/laf.py:180-203,363-382 -- lie in [0, w_o] x [0, h_o].
+ * It is mapped to the image by normalize_laf on the octave and denormalize_laf on the image:
+ * a' = (a / min(h_o, w_o)) min(h, w), x' = (x (1 / w_o)) w, y' = (y (1 / h_o)) h.  The score is the
+ * refined value.  The best num per image over all octaves by (score descending, octave ascending, voxel
+ * index (d h_o + y) w_o + x ascending) go to lafs [n][num][2][3], scores [n][num] float32 and count [n]
+ * int32; the slots past count hold a zero frame and score 0.  The reference also cuts every octave to num
+ * before the inside test; that is not reproduced (they differ only when an octave has more than num
+ * extrema).  No two 26-neighbours are both strict maxima (or both minima), so an octave has at most
+ * 2 ceil(D / 2) ceil(h_o / 2) ceil(w_o / 2) candidates per image: the lists in the workspace are sized by
+ * that bound and cannot overflow; keys (score bits, octave and voxel) are unique per image and compacted
+ * with integer atomics.  1 <= num <= 8192; any workspace of rr_detect_scale_space_workspace_bytes will do.
+ * Errors: those of the pyramid's arguments, minima not 0 / 1, mr_size not positive, a bad num, more than
+ * 2^32 - 1 voxels per image, null pointers, a short workspace (RR_ENOSPACE).  n == 0 returns RR_OK. */
+int rr_scale_space_select(const float* resp, int n, int h, int w, int levels, double sigma, int min_size, int minima,
+                          double mr_size, int num, float* lafs, float* scores, int* count, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* The whole detector on one stream: rr_scale_pyramid, then per octave rr_response (kind RR_RESP_HARRIS,
+ * RR_RESP_GFTT or RR_RESP_HESSIAN on the n L planes with the level sigmas as its `sigmas`) or
+ * rr_dog_response (RR_RESP_DOG), then rr_scale_space_select: bit-identical to calling them one after the
+ * other.  The pyramid is at the (256-byte aligned) start of the workspace.
+ * rr_detect_scale_space_workspace_bytes returns 0 for arguments the detector refuses.
+ * Errors: those of the entries, an unknown kind, a non-finite k for Harris, an octave below 4 pixels for
+ * the three corner responses.  n == 0 returns RR_OK. */
+size_t rr_detect_scale_space_workspace_bytes(int n, int c, int h, int w, int levels, double sigma, int min_size);
+int rr_detect_scale_space(const void* x, int n, int c, int h, int w, int u8, int levels, double sigma, int min_size, int kind,
+                          double k, int minima, double mr_size, int num, float* lafs, float* scores, int* count,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* Keypoint description (rr_describe.hip): local-affine-frame (LAF) patches, the dominant gradient
  * orientation of a patch, the SIFT descriptor of a patch, and the three fused per keypoint.  Common
  * to the four entries: all arithmetic is float64 in one fixed order per output and rounded once to
