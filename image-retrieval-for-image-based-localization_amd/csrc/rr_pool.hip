@@ -18,12 +18,12 @@ __device__ __forceinline__ float powp(float x, float p, int ip) {
     return __powf(x, p);
 }
 
-// NaN-propagating clamp / max, the semantics of torch.clamp(min=eps) and
-// torch.max the reference pools use (pools.py:10-38): a NaN activation (an
-// overflowed fp16 chain) must reach the descriptor, where extract_vectors sees
-// it, instead of being replaced by eps (fmaxf drops a NaN operand).
+// NaN-propagating clamp / max (max_nan, rr_internal.h), the semantics of
+// torch.clamp(min=eps) and torch.max the reference pools use (pools.py:10-38):
+// a NaN activation (an overflowed fp16 chain) must reach the descriptor, where
+// extract_vectors sees it, instead of being replaced by eps (fmaxf drops a NaN
+// operand).
 __device__ __forceinline__ float clamp_min_nan(float v, float eps) { return v < eps ? eps : v; }
-__device__ __forceinline__ float max_nan(float a, float b) { return (a > b || a != a) ? a : b; }
 
 // The exponent of a GeM parameter living in device memory (a learnable
 // ``pool.p``, pools.py:34) is read by the kernel itself: no host read-back, so

@@ -142,7 +142,8 @@ const char* ragged_fill(RaggedTab& t, const void* const* srcs, const int* extent
     return nullptr;
 }
 
-// NHWC max-pool, 8 channels (16 B of bf16) per thread.
+// NHWC max-pool, 8 channels (16 B of bf16) per thread.  Both max-pool kernels reduce with
+// max_nan: a window that holds a NaN gives NaN, as torch.nn.functional.max_pool2d does.
 __global__ void k_maxpool_nhwc_bf16x8(const uint4* __restrict__ x, int n, int h, int w, int c8, int k, int stride,
                                       int pad, uint4* __restrict__ y, int ho, int wo) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -168,8 +169,8 @@ __global__ void k_maxpool_nhwc_bf16x8(const uint4* __restrict__ x, int n, int h,
             const unsigned u[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                m[2 * e] = fmaxf(m[2 * e], __uint_as_float(u[e] << 16));
-                m[2 * e + 1] = fmaxf(m[2 * e + 1], __uint_as_float(u[e] & 0xffff0000u));
+                m[2 * e] = max_nan(m[2 * e], __uint_as_float(u[e] << 16));
+                m[2 * e + 1] = max_nan(m[2 * e + 1], __uint_as_float(u[e] & 0xffff0000u));
             }
         }
     }
@@ -202,7 +203,7 @@ __global__ void k_maxpool_nhwc(const T* __restrict__ x, int n, int h, int w, int
         for (int b = 0; b < k; ++b) {
             int ww = w0 + b;
             if (ww < 0 || ww >= w) continue;
-            m = fmaxf(m, DT<T>::to_f(x[(((long long)img * h + hh) * w + ww) * c + ch]));
+            m = max_nan(m, DT<T>::to_f(x[(((long long)img * h + hh) * w + ww) * c + ch]));
         }
     }
     y[i] = DT<T>::from_f(m);
@@ -517,6 +518,11 @@ int rr_resize_bilinear(const float* src, int c, int h, int w, float* dst, int ho
                        double scale_w, void* stream) {
     long long total = (long long)c * ho * wo;
     if (total <= 0) return fail(RR_EINVAL, "rr_resize_bilinear: empty");
+    // interpolate's rule, per axis: an axis whose output extent equals its input extent is
+    // sampled at scale 1 (source index = output index) whatever the scale factor and whatever
+    // the other axis does (a 2 x 3 plane "resized" by sqrt(2) becomes 2 x 4: rows are kept)
+    if (ho == h) scale_h = 1.0;
+    if (wo == w) scale_w = 1.0;
     const long long nb = (total + 255) / 256;
     hipLaunchKernelGGL(k_resize_bilinear, dim3((unsigned)(nb < (1ll << 22) ? nb : (1ll << 22))), dim3(256), 0,
                        as_stream(stream), src, c, h, w, dst,
