@@ -114,6 +114,13 @@ _SIGS = {
     "rr_sift_describe": ([_vp, _ll, _i, _i, _i, _i, _d, _vp, _vp], _i),
     "rr_describe_keypoints": ([_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _d, _vp, _i, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp,
                                _vp, _sz, _vp], _i),
+    "rr_pyrdown": ([_vp, _i, _i, _i, _i, _vp, _vp], _i),
+    "rr_patch_pyramid_bytes": ([_i, _i, _i, _i, _i, ctypes.POINTER(_i)], _sz),
+    "rr_patch_pyramid": ([_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp], _i),
+    "rr_extract_patches_pyramid": ([_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "rr_describe_pyramid_workspace_bytes": ([_i, _i, _i, _i, _i, _i, _i, _i], _sz),
+    "rr_describe_keypoints_pyramid": ([_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _d, _vp, _i, _i, _i, _i, _i, _i, _d, _vp, _vp,
+                                       _vp, _vp, _sz, _vp], _i),
     "rr_rank_workspace_bytes": ([_ll, _i], _sz),
     "rr_rank_full": ([_vp, _ll, _vp, _i, _i, _vp, _vp, _sz, _vp], _i),
     "rr_set_tuning": ([_i, _i], _i),

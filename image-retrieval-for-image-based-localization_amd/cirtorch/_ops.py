@@ -1128,9 +1128,84 @@ def sift_describe(patches, num_ang_bins=8, num_spatial_bins=4, rootsift=True, cl
     return out
 
 
+def pyramid_levels(h, w, ps):
+    """[(h_l, w_l)] of levels 0 .. last_level of the patch pyramid: level l is (h >> l, w >> l) while
+    its smaller side is at least ps (level 0 always exists).  Host arithmetic, as rr_patch_pyramid_bytes."""
+    out = [(int(h), int(w))]
+    while min(out[-1][0] // 2, out[-1][1] // 2) >= ps:
+        out.append((out[-1][0] // 2, out[-1][1] // 2))
+    return out
+
+
+def pyrdown(x):
+    """rr_pyrdown: float32 [B, C, H, W], H, W >= 3 -> [B, C, H // 2, W // 2].  No synchronisation."""
+    E.require_gpu(x)
+    _no_grad("pyrdown", x)
+    if x.dim() != 4:
+        raise ValueError("Invalid input shape, we expect BxCxHxW. Got: {}".format(tuple(x.shape)))
+    if not x.is_floating_point():
+        raise TypeError("pyrdown: a floating-point image, got %s" % x.dtype)
+    n, c, h, w = x.shape
+    if h < 3 or w < 3:
+        raise ValueError("pyrdown: H and W must be at least 3 (reflect padding by 2), got %d x %d" % (h, w))
+    x = x.float().contiguous()
+    out = torch.empty((n, c, h // 2, w // 2), dtype=torch.float32, device=x.device)
+    E.check(E.lib().rr_pyrdown(E.ptr(x), n, c, h, w, E.ptr(out), _st()), "rr_pyrdown")
+    return out
+
+
+def patch_pyramid(x, ps=32, gray=False):
+    """rr_patch_pyramid: levels 1 .. last of x [B, C, H, W] float32 or uint8 as a list of float32
+    [B, C or 1, H_l, W_l] views of one buffer (empty when the image has no level 1), and the buffer."""
+    x = _describe_image(x, "patch_pyramid")
+    _no_grad("patch_pyramid", x)
+    n, c, h, w = x.shape
+    if gray and c != 3:
+        raise ValueError("patch_pyramid: gray needs C == 3, got %d" % c)
+    ps = _patch_size(ps, "patch_pyramid")
+    co = 1 if gray else c
+    nbytes = int(E.lib().rr_patch_pyramid_bytes(n, co, h, w, ps, None))
+    buf = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=x.device)
+    E.check(E.lib().rr_patch_pyramid(E.ptr(x), n, c, h, w, int(x.dtype == torch.uint8), int(bool(gray)), ps, E.ptr(buf), nbytes,
+                                     _st()), "rr_patch_pyramid")
+    views, off = [], 0
+    for hl, wl in pyramid_levels(h, w, ps)[1:] if n else []:
+        views.append(buf[off:off + n * co * hl * wl].view(n, co, hl, wl))
+        off += n * co * hl * wl
+    return views, buf
+
+
+def extract_patches_pyramid(x, lafs, ps=32, gray=False, return_levels=False, pyr=None):
+    """rr_patch_pyramid + rr_extract_patches_pyramid: as extract_patches, every frame from its pyramid
+    level, a frame past the last level from the last.  With return_levels also the unclamped levels
+    int32 [B, N] and the flag int32 [1] (1 when a frame was clamped).  pyr: the buffer patch_pyramid
+    returned for the same (x, ps, gray).  No synchronisation."""
+    x = _describe_image(x, "extract_patches_pyramid")
+    E.require_gpu(lafs)
+    _no_grad("extract_patches_pyramid", x, lafs)
+    n, c, h, w = x.shape
+    if lafs.dim() != 4 or lafs.shape[0] != n or tuple(lafs.shape[2:]) != (2, 3):
+        raise ValueError("extract_patches_pyramid: lafs must be [%d, N, 2, 3], got %s" % (n, tuple(lafs.shape)))
+    if gray and c != 3:
+        raise ValueError("extract_patches_pyramid: gray needs C == 3, got %d" % c)
+    ps = _patch_size(ps, "extract_patches_pyramid")
+    lafs = lafs.float().contiguous()
+    npts = lafs.shape[1]
+    if pyr is None:
+        pyr = patch_pyramid(x, ps, gray)[1]
+    out = torch.empty((n, npts, 1 if gray else c, ps, ps), dtype=torch.float32, device=x.device)
+    levels = torch.empty((n, npts), dtype=torch.int32, device=x.device) if return_levels else None
+    flag = torch.empty(1, dtype=torch.int32, device=x.device) if return_levels else None
+    E.check(E.lib().rr_extract_patches_pyramid(E.ptr(x), n, c, h, w, int(x.dtype == torch.uint8), int(bool(gray)), E.ptr(pyr),
+                                               E.ptr(lafs), npts, ps, E.ptr(out), E.ptr(levels), E.ptr(flag), _st()),
+            "rr_extract_patches_pyramid")
+    return (out, levels, flag) if return_levels else out
+
+
 def describe_keypoints(x, kpts=None, count=None, scale=12.0, lafs=None, orient=False, orient_bins=36, ps=32, num_ang_bins=8,
-                       num_spatial_bins=4, rootsift=True, clipval=0.2, return_lafs=False):
-    """rr_describe_keypoints: x [B, 1|3, H, W] float32 or uint8, kpts [B, N, 2] pixel (x, y) (or
+                       num_spatial_bins=4, rootsift=True, clipval=0.2, return_lafs=False, pyramid=False):
+    """rr_describe_keypoints (rr_describe_keypoints_pyramid with pyramid): x [B, 1|3, H, W] float32 or
+    uint8, kpts [B, N, 2] pixel (x, y) (or
     lafs [B, N, 2, 3]), count int32 [B] or None -> (desc float32 [B, N, dim], angles float32 [B, N])
     and, with return_lafs, the described frames [B, N, 2, 3].  No synchronisation."""
     x = _describe_image(x, "describe_keypoints")
@@ -1165,6 +1240,13 @@ def describe_keypoints(x, kpts=None, count=None, scale=12.0, lafs=None, orient=F
     desc = torch.empty((n, npts, nb * ns * ns), dtype=torch.float32, device=dev)
     angles = torch.empty((n, npts), dtype=torch.float32, device=dev)
     lafs_out = torch.empty((n, npts, 2, 3), dtype=torch.float32, device=dev) if return_lafs else None
+    if pyramid:
+        ws = torch.empty(int(E.lib().rr_describe_pyramid_workspace_bytes(n, c, h, w, npts, ps, nb, ns)), dtype=torch.uint8, device=dev)
+        E.check(E.lib().rr_describe_keypoints_pyramid(E.ptr(x), n, c, h, w, int(x.dtype == torch.uint8), E.ptr(kpts), E.ptr(count),
+                                                      npts, float(scale), E.ptr(lafs), int(bool(orient)), int(orient_bins), ps, nb,
+                                                      ns, int(bool(rootsift)), float(clipval), E.ptr(desc), E.ptr(angles),
+                                                      E.ptr(lafs_out), E.ptr(ws), ws.numel(), _st()), "rr_describe_keypoints_pyramid")
+        return (desc, angles, lafs_out) if return_lafs else (desc, angles)
     ws = torch.empty(int(E.lib().rr_describe_workspace_bytes(n, npts, ps, nb, ns)), dtype=torch.uint8, device=dev)
     E.check(E.lib().rr_describe_keypoints(E.ptr(x), n, c, h, w, int(x.dtype == torch.uint8), E.ptr(kpts), E.ptr(count), npts,
                                           float(scale), E.ptr(lafs), int(bool(orient)), int(orient_bins), ps, nb, ns,

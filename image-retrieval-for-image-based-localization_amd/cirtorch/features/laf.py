@@ -7,11 +7,12 @@ the reference.  ``extract_patches_simple`` replaces ``F.affine_grid`` + ``F.grid
 border, ``align_corners=False``) by one kernel that reads pixels and writes patches, float32 or
 uint8 images (a uint8 pixel counts as ``v / 255``).
 
-``extract_patches_from_pyramid`` supports pyramid level 0 only: while ``2 * scale / PS < sqrt(2)``
-for every frame it equals the simple extraction, which is what it runs; a larger frame would need
-the blurred, down-sampled levels (``pyrdown``), which are not built, and raises
-NotImplementedError.  That check reads one flag from the device.  ``ellipse_to_laf`` and the
-drawing helpers are not built.
+``extract_patches_from_pyramid`` builds the ``pyrdown`` levels of the image (rr_patch_pyramid) and
+samples every frame from its level (rr_extract_patches_pyramid); while ``2 * scale / PS < sqrt(2)``
+that is level 0 and the bits are those of the simple extraction.  A frame past the last level
+raises NotImplementedError by default (that check reads one value from the device) or, with
+``beyond="clamp"``, is sampled from the last level.  ``ellipse_to_laf`` and the drawing helpers are
+not built.
 """
 
 import math
@@ -141,16 +142,26 @@ def extract_patches_simple(img, laf, PS=32, normalize_lafs_before_extraction=Tru
     return _ops.extract_patches(img, _pixel_lafs(img, laf, normalize_lafs_before_extraction), PS)
 
 
-def extract_patches_from_pyramid(img, laf, PS=32, normalize_lafs_before_extraction=True):
+def extract_patches_from_pyramid(img, laf, PS=32, normalize_lafs_before_extraction=True, beyond="raise"):
     """
-        Patches [B, N, C, PS, PS] of the LAFs from pyramid level 0; frames that belong to a higher
-        level (2 * scale / PS >= sqrt(2)) raise NotImplementedError.
+        Patches [B, N, C, PS, PS] of the LAFs, each sampled from the pyrdown level whose pixel pitch
+        matches the patch's: level max(0, floor(log2(2 * scale / PS) + 0.5)).  Levels exist while
+        their smaller side is at least PS.  A frame of a level past the last one raises
+        NotImplementedError with beyond="raise" (one value is read from the device for that) and is
+        sampled from the last level with beyond="clamp" (no synchronisation); the reference leaves
+        a zero patch there.
     """
+    if beyond not in ("raise", "clamp"):
+        raise ValueError("beyond must be 'raise' or 'clamp'. Got {!r}".format(beyond))
     plaf = _pixel_lafs(img, laf, normalize_lafs_before_extraction)
-    if plaf.numel() and bool(((2.0 * get_laf_scale(plaf) / float(PS)).log2() + 0.5 >= 1.0).any()):
-        raise NotImplementedError("extract_patches_from_pyramid: a frame with 2 * scale / PS >= sqrt(2) belongs to "
-                                  "pyramid level 1 or above; only level 0 is built")
-    return _ops.extract_patches(img, plaf, PS)
+    if beyond == "raise" and plaf.numel():
+        last = len(_ops.pyramid_levels(img.size(2), img.size(3), int(PS))) - 1
+        top = int(((2.0 * get_laf_scale(plaf.double()) / float(PS)).log2() + 0.5).floor().clamp(min=0).nan_to_num(0.0).max())
+        if top > last:
+            raise NotImplementedError("extract_patches_from_pyramid: a frame belongs to pyramid level {} but a {} x {} "
+                                      "image has levels 0..{} at PS {} (pass beyond='clamp' to sample the last level)"
+                                      .format(top, img.size(2), img.size(3), last, PS))
+    return _ops.extract_patches_pyramid(img, plaf, PS)
 
 
 def laf_to_boundary_points(LAF, n_pts=50):

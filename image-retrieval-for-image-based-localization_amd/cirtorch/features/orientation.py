@@ -4,8 +4,10 @@ kernels (rr_patch_orientation, rr_extract_patches).
 Same names, arguments, shape checks and error types.  ``PatchDominantGradientOrientation`` is one
 kernel (float32 patches; other floating dtypes are converted first): Sobel gradients, the
 soft-binned orientation histogram (the mean over the patch, no Gaussian weight -- the reference
-builds one and never applies it), circular smoothing and the argmax stay in LDS.  ``LAFOrienter`` extracts the patches of the frames it is given (pyramid level 0
-only, see ``laf.extract_patches_from_pyramid``), estimates the angles and returns
+builds one and never applies it), circular smoothing and the argmax stay in LDS.  ``LAFOrienter``
+extracts the patches of the frames it is given from their pyramid levels
+(``laf.extract_patches_from_pyramid`` with ``beyond="clamp"``: a frame larger than the last level
+allows is sampled from the last level), estimates the angles and returns
 ``make_upright(laf)`` rotated by them.  ``cirtorch.search.describe_keypoints`` does all of that and
 the descriptor in one launch.
 """
@@ -57,8 +59,8 @@ class PatchDominantGradientOrientation(nn.Module):
 
 class LAFOrienter(nn.Module):
     """
-        Gives every LAF its dominant gradient orientation: the patch of the frame (pyramid level 0)
-        goes through :class:`PatchDominantGradientOrientation`, and ``make_upright(laf)`` turned by
+        Gives every LAF its dominant gradient orientation: the patch of the frame (from its pyramid
+        level) goes through :class:`PatchDominantGradientOrientation`, and ``make_upright(laf)`` turned by
         that angle is returned
     """
 
@@ -77,7 +79,7 @@ class LAFOrienter(nn.Module):
         if laf.size(0) != img.size(0):
             raise ValueError("Batch size of laf and img should be the same. Got {}, {}".format(img.size(0), laf.size(0)))
         B, N = laf.shape[:2]
-        patches = extract_patches_from_pyramid(img, laf, self.patch_size).view(-1, 1, self.patch_size, self.patch_size)
+        patches = extract_patches_from_pyramid(img, laf, self.patch_size, beyond="clamp").view(-1, 1, self.patch_size, self.patch_size)
         angles = self.angle_detector(patches).view(B, N)
         rot = _rotation(rad2deg(angles))
         return torch.cat([torch.matmul(make_upright(laf)[..., :2, :2], rot), laf[..., :2, 2:]], dim=3)

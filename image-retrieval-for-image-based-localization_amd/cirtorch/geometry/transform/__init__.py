@@ -1,1 +1,1 @@
-from .pyramid import ScalePyramid  # noqa: F401
+from .pyramid import PyrDown, ScalePyramid, pyrdown  # noqa: F401

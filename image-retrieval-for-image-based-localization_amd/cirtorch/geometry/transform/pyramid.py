@@ -4,7 +4,11 @@ the level before and rounded once to float32.
 
 Same constructor and outputs.  The reference's ``forward`` reads ``self.init_sigma`` and its detector
 ``self.scale_pyr.n_levels``, which its constructor never sets; both are set here.
-``double_image=True`` is not built; ``pyrdown`` / ``PyrDown`` are not ported.
+``double_image=True`` is not built.
+
+``pyrdown`` / ``PyrDown`` (``pyramid.py:161-196``) are one kernel (rr_pyrdown): the 5 x 5 binomial blur
+with reflect padding and the bilinear halving as a single separable 6-tap pass at stride 2.  Other
+border types and ``align_corners=True`` are not built.
 """
 
 import torch
@@ -46,3 +50,32 @@ class ScalePyramid(nn.Module):
         pixel_dists = [torch.full((B, self.levels + self.extra_levels), float(2 ** i), dtype=torch.float32).to(x.device)
                        for i in range(len(octs))]
         return pyr, sigmas, pixel_dists
+
+
+def pyrdown(input, border_type='reflect', align_corners=False):
+    """
+        Blurs a tensor and downsamples it.
+    """
+    return PyrDown(border_type, align_corners)(input)
+
+
+class PyrDown(nn.Module):
+    """
+        Blurs a tensor and downsamples it: [B, C, H, W] -> [B, C, H // 2, W // 2], float32 on the GPU
+    """
+
+    def __init__(self, border_type='reflect', align_corners=False):
+        super(PyrDown, self).__init__()
+        if border_type != 'reflect':
+            raise NotImplementedError("border_type {!r} is not built: the kernel pads by reflection".format(border_type))
+        if align_corners:
+            raise NotImplementedError("align_corners=True is not built")
+        self.border_type = border_type
+        self.align_corners = align_corners
+
+    def forward(self, input):
+        if not torch.is_tensor(input):
+            raise TypeError("Input type is not a torch.Tensor. Got {}".format(type(input)))
+        if not len(input.shape) == 4:
+            raise ValueError("Invalid input shape, we expect BxCxHxW. Got: {}".format(input.shape))
+        return _ops.pyrdown(input)

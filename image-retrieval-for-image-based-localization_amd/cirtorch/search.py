@@ -449,7 +449,7 @@ def detect_keypoints_scale_space(images, num_features=2048, response="hessian", 
 
 
 def describe_keypoints(images, kpts, count=None, scale=12.0, lafs=None, orientation=False, patch_size=32, num_ang_bins=8,
-                       num_spatial_bins=4, rootsift=True, clipval=0.2):
+                       num_spatial_bins=4, rootsift=True, clipval=0.2, pyramid=False):
     """SIFT descriptors of the keypoints of a batch of images in one call (rr_describe_keypoints):
     the patch of ``extract_patches_simple`` (``cirtorch/features/laf.py``), optionally the dominant
     gradient orientation of ``LAFOrienter`` (``cirtorch/features/orientation.py``, 36 bins) and the
@@ -466,15 +466,22 @@ def describe_keypoints(images, kpts, count=None, scale=12.0, lafs=None, orientat
             default), angles float32 [B, N] in radians (0 without orientation).  Slots at or past
             count and slots whose keypoint is (-1, -1) hold zeros.
 
-    Patches are sampled from the image itself (pyramid level 0; the reference's pyramid agrees
-    while 2 * scale / patch_size < sqrt(2)).  float64 arithmetic rounded once: bit-identical run to
-    run and independent of the batch.  No patch is written to memory and nothing waits for the
-    host: graph-capturable for fixed shapes.  No gradients."""
+    pyramid=False samples every patch from the image itself (pyramid level 0; the reference's
+    pyramid agrees while 2 * scale / patch_size < sqrt(2)).  pyramid=True
+    (rr_describe_keypoints_pyramid) first builds the ``pyrdown`` levels of the gray image and samples
+    each frame from level max(0, floor(log2(2 s / patch_size) + 0.5)) as
+    ``extract_patches_from_pyramid`` does -- what the frames of ``detect_keypoints_scale_space`` need;
+    a frame past the last level (the last whose smaller side is at least patch_size) is sampled from
+    the last level, where the reference leaves a zero patch.  Frames of level 0 give the same bits
+    either way.  float64 arithmetic rounded once: bit-identical run to run and independent of the
+    batch.  No patch is written to memory and nothing waits for the host: graph-capturable for
+    fixed shapes.  No gradients."""
     if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] not in (1, 3):
         raise ValueError("describe_keypoints: images are [B, 1, H, W] or [B, 3, H, W], got %s"
                          % (tuple(images.shape) if torch.is_tensor(images) else type(images),))
     return _ops.describe_keypoints(images, kpts, count, float(scale), lafs, bool(orientation), 36, int(patch_size),
-                                   int(num_ang_bins), int(num_spatial_bins), bool(rootsift), float(clipval))
+                                   int(num_ang_bins), int(num_spatial_bins), bool(rootsift), float(clipval),
+                                   pyramid=bool(pyramid))
 
 
 def _match_rows(x):

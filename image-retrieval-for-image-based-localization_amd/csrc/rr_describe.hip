@@ -37,6 +37,17 @@
 //              weight computed in float64 and rounded to float32); the pooling kernel holds the
 //              float32 values (xc[ky] xc[kx]) / (ksize / 2)^2 of get_sift_pooling_kernel.
 //
+// The patch pyramid (pyrdown of cirtorch/geometry/transform/pyramid.py:161-196 and
+// extract_patches_from_pyramid of laf.py:311-360): level l + 1 is level l under the 5 x 5 binomial
+// blur (reflect padding by 2) and the bilinear halving, which together are one separable 6-tap pass
+// [1, 5, 10, 10, 5, 1] / 32 at stride 2 on the plane reflect-padded by 2.  k_pyrdown: one block of
+// 256 threads per output tile of 32 x 16; the 68 x 36 input tile goes to LDS once as doubles, even
+// and odd columns apart, so that the pass along x reads consecutive doubles (8-byte reads, no bank
+// conflict), its result stays in LDS and the pass along y reads that: a level is read once apart
+// from the halos, the next is written once, no half-filtered plane exists in memory.  A frame of
+// scale s is sampled from level max(0, floor(log2(2 s / ps) + 0.5)), clamped to the last level
+// whose smaller side is at least ps, after the frame is renormalised to the level's size.
+//
 // Bin sums by fixed lanes instead of atomics are what makes a descriptor a function of its patch
 // alone: not of the batch, the slot, the launch or the run.
 #include "rr_internal.h"
@@ -80,8 +91,8 @@ struct Frame {
 };
 
 // pixel i = row * ps + col of the patch of frame f
-template <bool U8>
-__device__ __forceinline__ float q_sample(const void* src, long long hw, int h, int w, int gray, const Frame& f, bool ok,
+template <bool U8, typename F>
+__device__ __forceinline__ float q_sample(const void* src, long long hw, int h, int w, int gray, const F& f, bool ok,
                                           int ps, int i) {
     if (!ok) return 0.f;
     const int r = i / ps, c = i - r * ps;
@@ -98,6 +109,94 @@ __device__ __forceinline__ float q_sample(const void* src, long long hw, int h, 
     const double val = ((p00 * ((1.0 - fx) * (1.0 - fy)) + p01 * (fx * (1.0 - fy))) + p10 * ((1.0 - fx) * fy)) + p11 * (fx * fy);
     return (float)val;
 }
+
+// ---- pyramid levels
+struct FrameD { double a00, a01, a02, a10, a11, a12; };
+
+// the level of a frame (laf.py:327-329): max(0, floor(log2(2 s / ps) + 0.5)), s = sqrt(|det + 1e-10|)
+__device__ __forceinline__ int q_level(const Frame& f, int ps) {
+    const double s = sqrt(fabs(((double)f.a00 * (double)f.a11 - (double)f.a10 * (double)f.a01) + 1e-10));
+    const double t = floor(log2((2.0 * s) / (double)ps) + 0.5);
+    return t >= 1.0 ? (t > 62.0 ? 62 : (int)t) : 0;   // a NaN: level 0
+}
+
+// Patch of frame f -> dst[ps ps] (LDS or global), from the level of f: level 0 is the image (src0),
+// level l >= 1 the float32 plane pl of `planes` planes per level in pyr (levels 1 .. last back to
+// back, level l of size (h >> l) x (w >> l)); a level past `last` is sampled from `last`.  The frame
+// on a level (normalize_laf / denormalize_laf of laf.py:219-257): the centre times (w_l / w, h_l / h),
+// the 2 x 2 part times min(h_l, w_l) / min(h, w), float64.  Returns the unclamped level.
+template <bool U8>
+__device__ __forceinline__ int q_patch(float* __restrict__ dst, const void* src0, long long hw, int h, int w, int gray,
+                                       const float* __restrict__ pyr, long long planes, long long pl, int last,
+                                       const Frame& f, int ps) {
+    const bool ok = f.finite();
+    const int lv = ok ? q_level(f, ps) : 0;
+    const int l = lv < last ? lv : last;
+    if (l <= 0) {
+        for (int i = threadIdx.x; i < ps * ps; i += Q_TB) dst[i] = q_sample<U8>(src0, hw, h, w, gray, f, ok, ps, i);
+        return lv;
+    }
+    long long off = 0;
+    for (int k = 1; k < l; ++k) off += planes * ((long long)(h >> k) * (long long)(w >> k));
+    const int hl = h >> l, wl = w >> l;
+    const float* src = pyr + off + pl * ((long long)hl * wl);
+    const double m = (double)(hl < wl ? hl : wl) / (double)(h < w ? h : w);
+    const double rx = (double)wl / (double)w, ry = (double)hl / (double)h;
+    const FrameD g{(double)f.a00 * m, (double)f.a01 * m, (double)f.a02 * rx, (double)f.a10 * m, (double)f.a11 * m, (double)f.a12 * ry};
+    for (int i = threadIdx.x; i < ps * ps; i += Q_TB) dst[i] = q_sample<false>(src, 0, hl, wl, 0, g, ok, ps, i);
+    return lv;
+}
+
+__device__ __forceinline__ int qreflecti(int v, int size) {   // reflect without the edge sample, then clamped
+    return qclampi(v < 0 ? -v : (v >= size ? 2 * size - 2 - v : v), size - 1);
+}
+
+constexpr int P_T = 32, P_TY = 16;       // output tile: 32 wide, 16 tall (28 KiB of LDS: five blocks per CU)
+constexpr int P_IN = 2 * P_T + 4;       // input tile with its halo: 68 columns
+constexpr int P_INY = 2 * P_TY + 4;     // and 36 rows
+constexpr int P_HALF = P_IN / 2;        // even (or odd) columns of an input row: 34
+
+// out[i][j] = sum_a sum_b c6[a] c6[b] xpad[2 i + a][2 j + b], c6 = [1, 5, 10, 10, 5, 1] / 32, xpad the plane
+// reflect-padded by 2; along x then along y, each sum in ascending tap order.  One block per tile of
+// one plane; gray: the input plane is three planes hw apart reduced on the fly (level 1 of a colour image).
+template <bool U8>
+__global__ void __launch_bounds__(Q_TB) k_pyrdown(const void* __restrict__ x, int h, int w, int gray, unsigned tiles_x,
+                                                  unsigned tiles, float* __restrict__ out) {
+    __shared__ double tile[P_INY * P_IN];   // row ly: the even columns, then the odd columns
+    __shared__ double mid[P_INY * P_T];     // filtered along x
+    const int tid = threadIdx.x;
+    const int h2 = h >> 1, w2 = w >> 1;
+    const unsigned pl = blockIdx.x / tiles, t = blockIdx.x - pl * tiles;
+    const int oy0 = (int)(t / tiles_x) * P_TY, ox0 = (int)(t % tiles_x) * P_T;
+    const long long hw = (long long)h * w;
+    const long long base = (long long)pl * (gray ? 3 * hw : hw);
+#pragma unroll 4
+    for (int i = tid; i < P_INY * P_IN; i += Q_TB) {
+        const int ly = i / P_IN, r = i - ly * P_IN;
+        const int odd = r >= P_HALF, lx = 2 * (r - odd * P_HALF) + odd;
+        const long long o = base + (long long)qreflecti(2 * oy0 - 2 + ly, h) * w + qreflecti(2 * ox0 - 2 + lx, w);
+        tile[i] = q_pixel<U8>(x, hw, o, gray);
+    }
+    __syncthreads();
+    const double c0 = 1.0 / 32.0, c1 = 5.0 / 32.0, c2 = 10.0 / 32.0;
+    for (int i = tid; i < P_INY * P_T; i += Q_TB) {
+        const int ly = i / P_T, ox = i - ly * P_T;
+        const double* e = tile + ly * P_IN + ox;
+        const double* o = e + P_HALF;
+        mid[i] = ((((c0 * e[0] + c1 * o[0]) + c2 * e[1]) + c2 * o[1]) + c1 * e[2]) + c0 * o[2];
+    }
+    __syncthreads();
+    for (int i = tid; i < P_TY * P_T; i += Q_TB) {
+        const int oy = i / P_T, ox = i - oy * P_T;
+        const int gy = oy0 + oy, gx = ox0 + ox;
+        if (gy >= h2 || gx >= w2) continue;
+        const double* c = mid + (2 * oy) * P_T + ox;
+        const double v = ((((c0 * c[0] + c1 * c[P_T]) + c2 * c[2 * P_T]) + c2 * c[3 * P_T]) + c1 * c[4 * P_T]) + c0 * c[5 * P_T];
+        out[(long long)pl * ((long long)h2 * w2) + (long long)gy * w2 + gx] = (float)v;
+    }
+}
+
+__global__ void k_clear_flag(int* flag) { *flag = 0; }
 
 // The block's LDS, carved from one dynamic allocation (lds_bytes below).
 struct Lds {
@@ -331,6 +430,28 @@ __global__ void __launch_bounds__(Q_TB) k_extract(const void* __restrict__ x, in
     for (int i = threadIdx.x; i < ps * ps; i += Q_TB) dst[i] = q_sample<U8>(src, hw, h, w, gray, f, ok, ps, i);
 }
 
+// the same from the frame's pyramid level; levels_out [n npts] (the unclamped level) and flag may be null
+template <bool U8>
+__global__ void __launch_bounds__(Q_TB) k_extract_pyr(const void* __restrict__ x, int c, int h, int w, int gray,
+                                                      const float* __restrict__ pyr, long long planes, int last,
+                                                      const float* __restrict__ lafs, int npts, int ps, float* __restrict__ out,
+                                                      int* __restrict__ levels_out, int* __restrict__ flag) {
+    const int co = gray ? 1 : c;
+    const long long slot = (long long)blockIdx.x / co;
+    const int ch = (int)((long long)blockIdx.x - slot * co);
+    const long long img = slot / npts, hw = (long long)h * w;
+    const long long plane = img * c + ch;
+    const void* src = U8 ? (const void*)(reinterpret_cast<const unsigned char*>(x) + plane * hw)
+                         : (const void*)(reinterpret_cast<const float*>(x) + plane * hw);
+    const float* fp = lafs + slot * 6;
+    const Frame f{fp[0], fp[1], fp[2], fp[3], fp[4], fp[5]};
+    const int lv = q_patch<U8>(out + (long long)blockIdx.x * ps * ps, src, hw, h, w, gray, pyr, planes, img * co + ch, last, f, ps);
+    if (threadIdx.x == 0 && ch == 0) {
+        if (levels_out) levels_out[slot] = lv;
+        if (flag && lv > last) *flag = 1;   // every writer stores the same value
+    }
+}
+
 __global__ void __launch_bounds__(Q_TB) k_orient(const float* __restrict__ patches, int ps, int nb, float* __restrict__ angle) {
     const Lds L = carve(q_lds, ps, 1, 1);
     const float* src = patches + (long long)blockIdx.x * ps * ps;
@@ -359,13 +480,15 @@ __device__ __forceinline__ void q_upright(const Frame& f, double& u00, double& u
     u11 = det * (det / b2a2);
 }
 
-// one block per keypoint slot
-template <bool U8>
+// one block per keypoint slot.  PYR: every patch comes from the pyramid level of the frame it is
+// sampled from (q_patch; pyr holds levels 1 .. last of the n gray planes), which is what keeps the
+// chain through rr_extract_patches_pyramid bit-identical; without PYR pyr, n and last are unused.
+template <bool U8, bool PYR>
 __global__ void __launch_bounds__(Q_TB) k_describe(const void* __restrict__ x, int c, int h, int w, const float* __restrict__ kpts,
                                                    const int* __restrict__ count, int npts, double scale,
                                                    const float* __restrict__ lafs, int orient, int obins, SiftArgs a,
                                                    float* __restrict__ desc, float* __restrict__ angles,
-                                                   float* __restrict__ lafs_out) {
+                                                   float* __restrict__ lafs_out, const float* __restrict__ pyr, int n, int last) {
     const int tid = threadIdx.x, dim = a.nb * a.ns * a.ns, ps = a.ps;
     const long long slot = blockIdx.x, img = slot / npts;
     const int pt = (int)(slot - img * npts);
@@ -397,8 +520,12 @@ __global__ void __launch_bounds__(Q_TB) k_describe(const void* __restrict__ x, i
         }
         // the upright frame IS its float32 rounding: the patch is sampled from it and it is what turns
         const double u00 = (double)f.a00, u10 = (double)f.a10, u11 = (double)f.a11;
-        const bool ok = f.finite();
-        for (int i = tid; i < ps * ps; i += Q_TB) L.patch[i] = q_sample<U8>(src, hw, h, w, gray, f, ok, ps, i);
+        if constexpr (PYR) {
+            q_patch<U8>(L.patch, src, hw, h, w, gray, pyr, n, img, last, f, ps);
+        } else {
+            const bool ok = f.finite();
+            for (int i = tid; i < ps * ps; i += Q_TB) L.patch[i] = q_sample<U8>(src, hw, h, w, gray, f, ok, ps, i);
+        }
         __syncthreads();
         ang = orient_phase(L, ps, obins);
         // upright . [[cos, sin], [-sin, cos]] (LAFOrienter's product), rounded once to float32
@@ -408,7 +535,9 @@ __global__ void __launch_bounds__(Q_TB) k_describe(const void* __restrict__ x, i
         f.a10 = (float)(u10 * cs - u11 * sn);
         f.a11 = (float)(u10 * sn + u11 * cs);
     }
-    {
+    if constexpr (PYR) {
+        q_patch<U8>(L.patch, src, hw, h, w, gray, pyr, n, img, last, f, ps);
+    } else {
         const bool ok = f.finite();
         for (int i = tid; i < ps * ps; i += Q_TB) L.patch[i] = q_sample<U8>(src, hw, h, w, gray, f, ok, ps, i);
     }
@@ -469,6 +598,50 @@ template <typename K> int want_lds(K kernel, size_t bytes, const std::string& w)
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
         (void)hipGetLastError();
         return fail(RR_EHIP, w + ": cannot reserve the patch's LDS");
+    }
+    return RR_OK;
+}
+
+size_t align256(size_t b) { return (b + 255) / 256 * 256; }
+
+// bytes of levels 1 .. last of n c planes of h x w (level l is (h >> l) x (w >> l): floor(h / 2) repeated),
+// last = the largest l with min(h_l, w_l) >= ps, 0 when there is none or an argument is out of range
+size_t pyramid_bytes(int n, int c, int h, int w, int ps, int& last) {
+    last = 0;
+    if (n < 1 || c < 1 || h < 1 || w < 1 || ps < Q_MINPS || ps > Q_MAXPS || !q_pixels_ok(n, c, h, w)) return 0;
+    size_t px = 0;
+    for (int l = 1; l < 31 && ((h >> l) < (w >> l) ? (h >> l) : (w >> l)) >= ps; ++l) {
+        px += (size_t)(h >> l) * (size_t)(w >> l);
+        last = l;
+    }
+    return px * (size_t)n * (size_t)c * sizeof(float);
+}
+
+// one level: planes of h x w (gray: planes images of three channels) -> planes of (h / 2) x (w / 2)
+int launch_pyrdown(const std::string& nm, const void* x, long long planes, int h, int w, bool u8, bool gray, float* out,
+                   hipStream_t s) {
+    const int h2 = h >> 1, w2 = w >> 1;
+    const unsigned tiles_x = (unsigned)((w2 + P_T - 1) / P_T), tiles = tiles_x * (unsigned)((h2 + P_TY - 1) / P_TY);
+    const long long blocks = planes * (long long)tiles;
+    if (blocks > Q_MAXBLOCKS) return fail(RR_EINVAL, nm + ": more than 2^24 - 1 output tiles");
+    if (u8)
+        hipLaunchKernelGGL(k_pyrdown<true>, dim3((unsigned)blocks), dim3(Q_TB), 0, s, x, h, w, (int)gray, tiles_x, tiles, out);
+    else
+        hipLaunchKernelGGL(k_pyrdown<false>, dim3((unsigned)blocks), dim3(Q_TB), 0, s, x, h, w, (int)gray, tiles_x, tiles, out);
+    return RR_OK;
+}
+
+// levels 1 .. last into pyr, back to back; level 1 reads the image, level l + 1 reads level l
+int build_pyramid(const std::string& nm, const void* x, int n, int c, int h, int w, bool u8, bool gray, int last, float* pyr,
+                  hipStream_t s) {
+    const long long planes = (long long)n * (gray ? 1 : c);
+    const void* src = x;
+    float* dst = pyr;
+    for (int l = 1; l <= last; ++l) {
+        const int rc = launch_pyrdown(nm, src, planes, h >> (l - 1), w >> (l - 1), l == 1 && u8, l == 1 && gray, dst, s);
+        if (rc) return rc;
+        src = dst;
+        dst += planes * ((long long)(h >> l) * (long long)(w >> l));
     }
     return RR_OK;
 }
@@ -537,11 +710,11 @@ int rr_sift_describe(const float* patches, long long B, int ps, int num_ang_bins
     return check_launch("rr_sift_describe");
 }
 
-int rr_describe_keypoints(const void* x, int n, int c, int h, int w, int u8, const float* kpts, const int* count, int npts,
-                          double scale, const float* lafs, int orient, int orient_bins, int ps, int num_ang_bins,
-                          int num_spatial_bins, int rootsift, double clipval, float* desc, float* angles, float* lafs_out,
-                          void* workspace, size_t workspace_bytes, void* stream) {
-    const std::string nm("rr_describe_keypoints");
+// both describe entries: pyramid = the levels are built at the start of the workspace first
+static int describe(const std::string& nm, bool pyramid, const void* x, int n, int c, int h, int w, int u8, const float* kpts,
+                    const int* count, int npts, double scale, const float* lafs, int orient, int orient_bins, int ps,
+                    int num_ang_bins, int num_spatial_bins, int rootsift, double clipval, float* desc, float* angles,
+                    float* lafs_out, void* workspace, size_t workspace_bytes, void* stream) {
     if (c != 1 && c != 3) return fail(RR_EINVAL, nm + ": c must be 1 or 3");
     int rc = check_image(nm, x, n, c, h, w);
     if (rc) return rc;
@@ -556,21 +729,121 @@ int rr_describe_keypoints(const void* x, int n, int c, int h, int w, int u8, con
     const long long blocks = (long long)n * npts;
     if (blocks > Q_MAXBLOCKS) return fail(RR_EINVAL, nm + ": more than 2^24 - 1 keypoint slots");
     if (blocks > 0 && ((!kpts && !lafs) || !desc)) return fail(RR_EINVAL, nm + ": null keypoints or output");
-    if (!workspace || workspace_bytes < Q_WS) return fail(RR_ENOSPACE, nm + ": workspace too small");
+    int last = 0;
+    const size_t pyr_bytes = pyramid ? pyramid_bytes(n, 1, h, w, ps, last) : 0;
+    if (!workspace || workspace_bytes < Q_WS + align256(pyr_bytes)) return fail(RR_ENOSPACE, nm + ": workspace too small");
     if (blocks == 0) return RR_OK;
-    const size_t lds = lds_bytes(ps, a.nb * a.ns * a.ns, a.ksize);
-    if (u8) {
-        rc = want_lds(k_describe<true>, lds, nm);
+    const float* pyr = reinterpret_cast<const float*>(workspace);
+    if (pyramid && last > 0) {
+        rc = build_pyramid(nm, x, n, c, h, w, u8 != 0, c == 3, last, reinterpret_cast<float*>(workspace), as_stream(stream));
         if (rc) return rc;
-        hipLaunchKernelGGL(k_describe<true>, dim3((unsigned)blocks), dim3(Q_TB), lds, as_stream(stream), x, c, h, w, kpts, count, npts,
-                           scale, lafs, orient, orient_bins, a, desc, angles, lafs_out);
-    } else {
-        rc = want_lds(k_describe<false>, lds, nm);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_describe<false>, dim3((unsigned)blocks), dim3(Q_TB), lds, as_stream(stream), x, c, h, w, kpts, count, npts,
-                           scale, lafs, orient, orient_bins, a, desc, angles, lafs_out);
     }
-    return check_launch("rr_describe_keypoints");
+    const size_t lds = lds_bytes(ps, a.nb * a.ns * a.ns, a.ksize);
+    const dim3 grid((unsigned)blocks), block(Q_TB);
+#define RR_DESCRIBE(U8, PYR)                                                                                          \
+    do {                                                                                                              \
+        rc = want_lds(k_describe<U8, PYR>, lds, nm);                                                                  \
+        if (rc) return rc;                                                                                            \
+        hipLaunchKernelGGL((k_describe<U8, PYR>), grid, block, lds, as_stream(stream), x, c, h, w, kpts, count, npts, \
+                           scale, lafs, orient, orient_bins, a, desc, angles, lafs_out, pyr, n, last);               \
+    } while (0)
+    if (pyramid) {
+        if (u8) RR_DESCRIBE(true, true); else RR_DESCRIBE(false, true);
+    } else {
+        if (u8) RR_DESCRIBE(true, false); else RR_DESCRIBE(false, false);
+    }
+#undef RR_DESCRIBE
+    return check_launch(nm.c_str());
+}
+
+int rr_describe_keypoints(const void* x, int n, int c, int h, int w, int u8, const float* kpts, const int* count, int npts,
+                          double scale, const float* lafs, int orient, int orient_bins, int ps, int num_ang_bins,
+                          int num_spatial_bins, int rootsift, double clipval, float* desc, float* angles, float* lafs_out,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    return describe("rr_describe_keypoints", false, x, n, c, h, w, u8, kpts, count, npts, scale, lafs, orient, orient_bins, ps,
+                    num_ang_bins, num_spatial_bins, rootsift, clipval, desc, angles, lafs_out, workspace, workspace_bytes, stream);
+}
+
+size_t rr_describe_pyramid_workspace_bytes(int n, int c, int h, int w, int npts, int ps, int num_ang_bins, int num_spatial_bins) {
+    (void)c; (void)npts; (void)num_ang_bins; (void)num_spatial_bins;
+    int last = 0;
+    return Q_WS + align256(pyramid_bytes(n, 1, h, w, ps, last));
+}
+
+int rr_describe_keypoints_pyramid(const void* x, int n, int c, int h, int w, int u8, const float* kpts, const int* count,
+                                  int npts, double scale, const float* lafs, int orient, int orient_bins, int ps,
+                                  int num_ang_bins, int num_spatial_bins, int rootsift, double clipval, float* desc,
+                                  float* angles, float* lafs_out, void* workspace, size_t workspace_bytes, void* stream) {
+    return describe("rr_describe_keypoints_pyramid", true, x, n, c, h, w, u8, kpts, count, npts, scale, lafs, orient, orient_bins,
+                    ps, num_ang_bins, num_spatial_bins, rootsift, clipval, desc, angles, lafs_out, workspace, workspace_bytes,
+                    stream);
+}
+
+size_t rr_patch_pyramid_bytes(int n, int c, int h, int w, int ps, int* last_level) {
+    int last = 0;
+    const size_t b = pyramid_bytes(n, c, h, w, ps, last);
+    if (last_level) *last_level = last;
+    return b;
+}
+
+int rr_pyrdown(const float* x, int n, int c, int h, int w, float* out, void* stream) {
+    const std::string nm("rr_pyrdown");
+    int rc = check_image(nm, x, n, c, h, w);
+    if (rc) return rc;
+    if (h < 3 || w < 3) return fail(RR_EINVAL, nm + ": h and w must be at least 3 (reflect padding by 2)");
+    if (n > 0 && !out) return fail(RR_EINVAL, nm + ": null output");
+    if (n == 0) return RR_OK;
+    rc = launch_pyrdown(nm, x, (long long)n * c, h, w, false, false, out, as_stream(stream));
+    return rc ? rc : check_launch("rr_pyrdown");
+}
+
+int rr_patch_pyramid(const void* x, int n, int c, int h, int w, int u8, int gray, int ps, float* pyr, size_t pyr_bytes,
+                     void* stream) {
+    const std::string nm("rr_patch_pyramid");
+    int rc = check_image(nm, x, n, c, h, w);
+    if (rc) return rc;
+    if (gray != 0 && gray != 1) return fail(RR_EINVAL, nm + ": gray must be 0 or 1");
+    if (gray && c != 3) return fail(RR_EINVAL, nm + ": gray needs c == 3");
+    if (ps < Q_MINPS || ps > Q_MAXPS) return fail(RR_EINVAL, nm + ": patch size outside [8, 64]");
+    int last = 0;
+    const size_t need = pyramid_bytes(n, gray ? 1 : c, h, w, ps, last);
+    if (need > 0 && !pyr) return fail(RR_EINVAL, nm + ": null pyramid buffer");
+    if (pyr_bytes < need) return fail(RR_ENOSPACE, nm + ": pyramid buffer too small");
+    if (need == 0) return RR_OK;
+    rc = build_pyramid(nm, x, n, c, h, w, u8 != 0, gray != 0, last, pyr, as_stream(stream));
+    return rc ? rc : check_launch("rr_patch_pyramid");
+}
+
+int rr_extract_patches_pyramid(const void* x, int n, int c, int h, int w, int u8, int gray, const float* pyr, const float* lafs,
+                               int npts, int ps, float* out, int* levels_out, int* beyond_flag, void* stream) {
+    const std::string nm("rr_extract_patches_pyramid");
+    int rc = check_image(nm, x, n, c, h, w);
+    if (rc) return rc;
+    if (gray != 0 && gray != 1) return fail(RR_EINVAL, nm + ": gray must be 0 or 1");
+    if (gray && c != 3) return fail(RR_EINVAL, nm + ": gray needs c == 3");
+    if (npts < 0) return fail(RR_EINVAL, nm + ": negative npts");
+    if (ps < Q_MINPS || ps > Q_MAXPS) return fail(RR_EINVAL, nm + ": patch size outside [8, 64]");
+    const int co = gray ? 1 : c;
+    const long long blocks = (long long)n * npts * co;
+    if (blocks > Q_MAXBLOCKS) return fail(RR_EINVAL, nm + ": more than 2^24 - 1 patches");
+    if (blocks > 0 && (!lafs || !out)) return fail(RR_EINVAL, nm + ": null frames or output");
+    int last = 0;
+    const size_t need = pyramid_bytes(n, co, h, w, ps, last);
+    if (blocks > 0 && need > 0 && !pyr) return fail(RR_EINVAL, nm + ": null pyramid buffer");
+    if (blocks == 0 && !beyond_flag) return RR_OK;
+    hipStream_t s = as_stream(stream);
+    // the flag is reset by a kernel, not hipMemsetAsync (captured memset nodes: DESIGN.md §4, kNN)
+    if (beyond_flag) hipLaunchKernelGGL(k_clear_flag, dim3(1), dim3(1), 0, s, beyond_flag);
+    if (blocks > 0) {
+        const long long planes = (long long)n * co;
+        if (u8)
+            hipLaunchKernelGGL(k_extract_pyr<true>, dim3((unsigned)blocks), dim3(Q_TB), 0, s, x, c, h, w, gray, pyr, planes, last, lafs,
+                               npts, ps, out, levels_out, beyond_flag);
+        else
+            hipLaunchKernelGGL(k_extract_pyr<false>, dim3((unsigned)blocks), dim3(Q_TB), 0, s, x, c, h, w, gray, pyr, planes, last, lafs,
+                               npts, ps, out, levels_out, beyond_flag);
+    }
+    return check_launch("rr_extract_patches_pyramid");
 }
 
 }  // extern "C"

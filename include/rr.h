@@ -726,6 +726,67 @@ int rr_describe_keypoints(const void* x, int n, int c, int h, int w, int u8, con
                           int num_spatial_bins, int rootsift, double clipval, float* desc, float* angles, float* lafs_out,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* The patch pyramid (rr_describe.hip): large frames are sampled from a blurred, halved level of the
+ * image instead of stepping over full-resolution pixels.  The rules of the four entries above hold:
+ * float64 in one fixed order per output, rounded once to float32, no atomic on a floating-point
+ * value, a result depends on its own frame and image only, argument errors before anything is
+ * enqueued, nothing is read back (levels, sizes and offsets are host arithmetic on (h, w, ps)),
+ * graph-capturable.
+ *
+ * rr_pyrdown is PyrDown.forward (cirtorch/geometry/transform/pyramid.py:161-196) with
+ * border_type 'reflect' and align_corners False: the 5 x 5 binomial kernel [1, 4, 6, 4, 1]^2 / 256 on
+ * the plane reflect-padded by 2, then F.interpolate(scale_factor=0.5, bilinear), which is the mean
+ * of the blurred pixels (2i, 2i+1) x (2j, 2j+1).  The two are one separable pass:
+ *   out[i][j] = sum_a sum_b c6[a] c6[b] xpad[2 i + a][2 j + b],  c6 = [1, 5, 10, 10, 5, 1] / 32,
+ *   xpad[k] = x[reflect(k - 2)], reflect(-1) = 1, reflect(size) = size - 2
+ * along x first, then along y, each sum in ascending tap order.  x [n][c][h][w] float32,
+ * out [n][c][h / 2][w / 2] (floor, odd sizes too).  h, w >= 3.  One block per output tile of 32 x 16 (w x h):
+ * the input tile and its halo are read once into LDS, the x pass stays in LDS, the output is written
+ * once.  Errors: null pointers, bad sizes, h or w < 3, more than 2^31 pixels, more than 2^24 - 1
+ * tiles.  n == 0 returns RR_OK.
+ *
+ * rr_patch_pyramid builds levels 1 .. last_level of extract_patches_from_pyramid
+ * (cirtorch/features/laf.py:311-360): level 0 is the image, level l + 1 = pyrdown(level l), of size
+ * (h >> l) x (w >> l); last_level is the largest l with min(h_l, w_l) >= ps (the reference's loop
+ * condition, laf.py:335), 0 when there is none.  Level 1 reads the image itself: float32, or uint8
+ * (float32(v) / 255.0f), and with gray = 1 (c == 3) the pixel (0.299 r + 0.587 g) + 0.114 b of
+ * rr_extract_patches; it stores c planes per image (one with gray).  pyr receives the levels back to
+ * back, level l as [n][c or 1][h_l][w_l] float32; rr_patch_pyramid_bytes is its size for c stored
+ * planes per image (pass 1 for gray) and writes last_level (may be NULL); it returns 0, last_level
+ * 0, for arguments out of range.  Errors: those of rr_extract_patches, a null or short buffer
+ * (RR_ENOSPACE).  Nothing to build returns RR_OK.
+ *
+ * rr_extract_patches_pyramid is rr_extract_patches with every frame sampled from its level:
+ *   s = sqrt(|(a00 a11 - a10 a01) + 1e-10|),  level = max(0, floor(log2((2 s) / ps) + 0.5))
+ * (laf.py:327-329), float64.  On level l >= 1 the frame is renormalised as normalize_laf /
+ * denormalize_laf do (laf.py:219-257): the centre becomes (a02 (w_l / w), a12 (h_l / h)), the 2 x 2
+ * part is multiplied by min(h_l, w_l) / min(h, w), all float64 and not rounded to float32, and the
+ * level's plane is sampled by the rule of rr_extract_patches.  Level 0 gives the bits of
+ * rr_extract_patches.  A frame whose level exceeds last_level is sampled from last_level: a
+ * deliberate deviation, the reference leaves a zero patch there (constant descriptors that match
+ * each other).  levels_out (NULL or int32 [n][npts]) receives the unclamped level (0 for a
+ * non-finite frame); beyond_flag (NULL or one device int) is cleared by the call and set to 1 when a
+ * frame was clamped.  pyr is what rr_patch_pyramid wrote for the same (x, gray, ps); it may be NULL
+ * when last_level is 0.
+ *
+ * rr_describe_keypoints_pyramid takes the arguments of rr_describe_keypoints, builds the gray
+ * pyramid at the start of the workspace (rr_describe_pyramid_workspace_bytes) and describes; every
+ * patch, the upright frame's and the described frame's, comes from the level of the frame it is
+ * sampled from.  desc is bit-identical to rr_patch_pyramid -> rr_extract_patches_pyramid on lafs_out
+ * -> rr_sift_describe, theta to rr_patch_orientation on the pyramid patches of the upright frames,
+ * and where every frame is of level 0 the bits are those of rr_describe_keypoints. */
+int rr_pyrdown(const float* x, int n, int c, int h, int w, float* out, void* stream);
+size_t rr_patch_pyramid_bytes(int n, int c, int h, int w, int ps, int* last_level);
+int rr_patch_pyramid(const void* x, int n, int c, int h, int w, int u8, int gray, int ps, float* pyr, size_t pyr_bytes,
+                     void* stream);
+int rr_extract_patches_pyramid(const void* x, int n, int c, int h, int w, int u8, int gray, const float* pyr, const float* lafs,
+                               int npts, int ps, float* out, int* levels_out, int* beyond_flag, void* stream);
+size_t rr_describe_pyramid_workspace_bytes(int n, int c, int h, int w, int npts, int ps, int num_ang_bins, int num_spatial_bins);
+int rr_describe_keypoints_pyramid(const void* x, int n, int c, int h, int w, int u8, const float* kpts, const int* count,
+                                  int npts, double scale, const float* lafs, int orient, int orient_bins, int ps,
+                                  int num_ang_bins, int num_spatial_bins, int rootsift, double clipval, float* desc,
+                                  float* angles, float* lafs_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Full ranking for any database size: out_idx[q][r] = the r-th database row of
  * query q by (float64 score desc, index asc) — np.argsort(-np.dot(vecs.T, qvecs),
  * axis=0) of scripts/test.py:247-248 as [nq][n] (rr_knn_topk ranks k <= 8192).
