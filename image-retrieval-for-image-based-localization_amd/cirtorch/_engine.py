@@ -121,7 +121,11 @@ _SIGS = {
     "rr_describe_pyramid_workspace_bytes": ([_i, _i, _i, _i, _i, _i, _i, _i], _sz),
     "rr_describe_keypoints_pyramid": ([_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _d, _vp, _i, _i, _i, _i, _i, _i, _d, _vp, _vp,
                                        _vp, _vp, _sz, _vp], _i),
-    "rr_rank_workspace_bytes": ([_ll, _i], _sz),
+    "rr_patch_affine_shape": ([_vp, _ll, _i, _d, _vp, _vp], _i),
+    "rr_ellipse_to_laf": ([_vp, _ll, _vp, _vp], _i),
+    "rr_laf_affine_shape_workspace_bytes": ([_i, _i, _i, _i, _i, _i], _sz),
+    "rr_laf_affine_shape": ([_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _d, _vp, _vp, _sz, _vp], _i),
+    "rr_rank_workspace_bytes":([_ll, _i], _sz),
     "rr_rank_full": ([_vp, _ll, _vp, _i, _i, _vp, _vp, _sz, _vp], _i),
     "rr_set_tuning": ([_i, _i], _i),
     "rr_fill_unit_rows": ([_vp, _ll, _i, ctypes.c_ulonglong, _ll, _vp], _i),

@@ -1253,3 +1253,62 @@ def describe_keypoints(x, kpts=None, count=None, scale=12.0, lafs=None, orient=F
                                           int(bool(rootsift)), float(clipval), E.ptr(desc), E.ptr(angles), E.ptr(lafs_out),
                                           E.ptr(ws), ws.numel(), _st()), "rr_describe_keypoints")
     return (desc, angles, lafs_out) if return_lafs else (desc, angles)
+
+
+# ---------------------------------------------------------------- affine shape
+def patch_affine_shape(patches, eps=1e-10):
+    """rr_patch_affine_shape: float32 patches [..., ps, ps] -> the normalised second-moment matrix
+    (a, b, c) float32 [..., 3], (1, 0, 1) where two of the raw moments are below eps.  No synchronisation."""
+    patches = _patches(patches, "patch_affine_shape")
+    ps = _patch_size(patches.shape[-1], "patch_affine_shape")
+    if not np.isfinite(float(eps)):
+        raise ValueError("patch_affine_shape: eps = %r must be finite" % (eps,))
+    lead = tuple(patches.shape[:-2])
+    out = torch.empty(lead + (3,), dtype=torch.float32, device=patches.device)
+    E.check(E.lib().rr_patch_affine_shape(E.ptr(patches), patches.numel() // (ps * ps), ps, float(eps), E.ptr(out), _st()),
+            "rr_patch_affine_shape")
+    return out
+
+
+def ellipse_to_laf(ells):
+    """rr_ellipse_to_laf: ellipses (x, y, a, b, c) [..., 5] -> float32 frames [..., 2, 3].  No synchronisation."""
+    E.require_gpu(ells)
+    _no_grad("ellipse_to_laf", ells)
+    if ells.dim() < 1 or ells.shape[-1] != 5 or not ells.is_floating_point():
+        raise RuntimeError("ellipse_to_laf: floating-point ellipses [..., 5], got %s %s" % (ells.dtype, tuple(ells.shape)))
+    ells = ells.float().contiguous()
+    out = torch.empty(tuple(ells.shape[:-1]) + (2, 3), dtype=torch.float32, device=ells.device)
+    E.check(E.lib().rr_ellipse_to_laf(E.ptr(ells), ells.numel() // 5, E.ptr(out), _st()), "rr_ellipse_to_laf")
+    return out
+
+
+def laf_affine_shape(x, lafs, count=None, ps=32, eps=1e-10, out=None):
+    """rr_laf_affine_shape: x [B, 1|3, H, W] float32 or uint8, lafs [B, N, 2, 3] float32 pixels, count
+    int32 [B] or None -> the frames with the affine shape of their patch and their own scale and
+    centre, float32 [B, N, 2, 3]; dead slots hold zeros.  out: a contiguous float32 tensor of that
+    shape to write to (it may be lafs itself).  No synchronisation."""
+    x = _describe_image(x, "laf_affine_shape")
+    n, c, h, w = x.shape
+    if c not in (1, 3):
+        raise ValueError("laf_affine_shape: images are [B, 1, H, W] or [B, 3, H, W], got C = %d" % c)
+    E.require_gpu(lafs, count, out)
+    _no_grad("laf_affine_shape", x, lafs)
+    if lafs.dim() != 4 or lafs.shape[0] != n or tuple(lafs.shape[2:]) != (2, 3):
+        raise ValueError("laf_affine_shape: lafs must be [%d, N, 2, 3], got %s" % (n, tuple(lafs.shape)))
+    lafs = lafs.float().contiguous()
+    npts = lafs.shape[1]
+    if count is not None:
+        if count.dim() != 1 or count.shape[0] != n or count.dtype != torch.int32:
+            raise ValueError("laf_affine_shape: count must be int32 [%d], got %s %s" % (n, count.dtype, tuple(count.shape)))
+        count = count.contiguous()
+    ps = _patch_size(ps, "laf_affine_shape")
+    if not np.isfinite(float(eps)):
+        raise ValueError("laf_affine_shape: eps = %r must be finite" % (eps,))
+    if out is None:
+        out = torch.empty((n, npts, 2, 3), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n, npts, 2, 3) or not out.is_contiguous():
+        raise ValueError("laf_affine_shape: out must be contiguous float32 [%d, %d, 2, 3]" % (n, npts))
+    ws = torch.empty(int(E.lib().rr_laf_affine_shape_workspace_bytes(n, c, h, w, npts, ps)), dtype=torch.uint8, device=x.device)
+    E.check(E.lib().rr_laf_affine_shape(E.ptr(x), n, c, h, w, int(x.dtype == torch.uint8), E.ptr(lafs), E.ptr(count), npts, ps,
+                                        float(eps), E.ptr(out), E.ptr(ws), ws.numel(), _st()), "rr_laf_affine_shape")
+    return out

@@ -11,8 +11,8 @@ uint8 images (a uint8 pixel counts as ``v / 255``).
 samples every frame from its level (rr_extract_patches_pyramid); while ``2 * scale / PS < sqrt(2)``
 that is level 0 and the bits are those of the simple extraction.  A frame past the last level
 raises NotImplementedError by default (that check reads one value from the device) or, with
-``beyond="clamp"``, is sampled from the last level.  ``ellipse_to_laf`` and the drawing helpers are
-not built.
+``beyond="clamp"``, is sampled from the last level.  ``ellipse_to_laf`` is one kernel
+(rr_ellipse_to_laf: the closed-form inverse, float32 frames).  The drawing helpers are not built.
 """
 
 import math
@@ -101,6 +101,17 @@ def make_upright(laf, eps=1e-9):
     row1 = torch.cat([(a11 * a01 + a10 * a00) / (b2a2 * det), det / b2a2], dim=3)
     unit = torch.cat([torch.cat([row0, row1], dim=2), laf[..., :, 2:3]], dim=3)
     return scale_laf(unit, det)
+
+
+def ellipse_to_laf(ells):
+    """
+        Ellipses (x, y, a, b, c) [B, N, 5] -> LAFs [B, N, 2, 3] (float32): the inverse of the
+        lower-triangular square root [[sqrt|a|, 0], [b / (sqrt|a| + sqrt|c|), sqrt|c|]], centre (x, y)
+    """
+    if not torch.is_tensor(ells) or len(ells.size()) != 3 or ells.size(2) != 5:
+        raise TypeError("ellipse shape should be must be [BxNx5]. Got {}"
+                        .format(ells.size() if torch.is_tensor(ells) else type(ells)))
+    return _ops.ellipse_to_laf(ells)
 
 
 def _size_coef(LAF, images):

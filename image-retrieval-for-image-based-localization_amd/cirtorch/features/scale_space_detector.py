@@ -5,7 +5,8 @@ quadratic refinement, frames and the best N per image in one call, nothing read 
 The constructor keeps the reference's arguments.  Built: ``ScalePyramid`` without ``double_image``,
 the responses ``BlobHessian``, ``CornerHarris``, ``CornerGFTT`` and ``BlobDoG``, ``ConvQuadInterp3d``
 as ``nms_module`` (the default here; the reference's default ``ConvSoftArgmax3d`` keeps every voxel),
-``PassLAF`` as ``aff_module``, ``PassLAF`` or ``LAFOrienter`` as ``ori_module``, no mask.  Only strict
+``PassLAF`` or ``LAFAffineShapeEstimator`` (Hessian-Affine; one pass, no iterated adaptation) as
+``aff_module``, ``PassLAF`` or ``LAFOrienter`` as ``ori_module``, no mask.  Only strict
 extrema become keypoints (the reference fills the list up with arbitrary voxels), each offset is
 applied to its own axis, the scores carry no ``strict_maxima_bonus``, and an octave is not cut to
 ``num_features`` before the inside test: see include/rr.h.
@@ -16,6 +17,7 @@ import torch.nn as nn
 from .. import _ops
 from ..geometry.subpix.spatial_soft_argmax import ConvQuadInterp3d
 from ..geometry.transform.pyramid import ScalePyramid
+from .affine_shape import LAFAffineShapeEstimator
 from .orientation import LAFOrienter, PassLAF
 from .responses import BlobDoG, BlobHessian, CornerGFTT, CornerHarris
 
@@ -42,8 +44,8 @@ class ScaleSpaceDetector(nn.Module):
             raise NotImplementedError("scale_pyr_module must be a ScalePyramid, got %s" % type(self.scale_pyr).__name__)
         if type(self.nms) is not ConvQuadInterp3d:
             raise NotImplementedError("nms_module must be a ConvQuadInterp3d, got %s" % type(self.nms).__name__)
-        if type(self.aff) is not PassLAF:
-            raise NotImplementedError("aff_module must be PassLAF (affine shape is not built), got %s" % type(self.aff).__name__)
+        if type(self.aff) not in (PassLAF, LAFAffineShapeEstimator):
+            raise NotImplementedError("aff_module must be PassLAF or LAFAffineShapeEstimator, got %s" % type(self.aff).__name__)
         if type(self.ori) not in (PassLAF, LAFOrienter):
             raise NotImplementedError("ori_module must be PassLAF or LAFOrienter, got %s" % type(self.ori).__name__)
         kinds = {BlobHessian: "hessian", CornerHarris: "harris", CornerGFTT: "gftt", BlobDoG: "dog"}

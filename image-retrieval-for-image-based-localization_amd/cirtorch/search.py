@@ -415,7 +415,7 @@ def detect_keypoints(images, num_features=2048, response="harris", k=0.04, nms=5
 
 
 def detect_keypoints_scale_space(images, num_features=2048, response="hessian", levels=3, sigma=1.6, min_size=15, mr_size=6.0,
-                                 minima=None, k=0.04):
+                                 minima=None, k=0.04, affine=False, affine_patch_size=32):
     """Scale-covariant keypoints of a batch of images in one call (rr_detect_scale_space): the
     ``ScalePyramid`` of ``cirtorch/geometry/transform/pyramid.py``, the Hessian, Harris, Shi-Tomasi
     ("gftt") or difference-of-Gaussians ("dog") response of every level, the strict 3 x 3 x 3 extrema
@@ -432,7 +432,10 @@ def detect_keypoints_scale_space(images, num_features=2048, response="hessian", 
 
     The best `num_features` are taken over all octaves by (score desc, octave asc, voxel asc).  With
     `minima` (default: only for "dog") strict minima count too, scored by -response.  A frame whose
-    circle of radius s leaves its octave is dropped.  float64 arithmetic rounded once: bit-identical
+    circle of radius s leaves its octave is dropped.  With `affine` the detected frames go through
+    ``estimate_affine_shape`` (patch size `affine_patch_size`) before they are returned: one more
+    call, in place, the scale and centre of every frame kept (Hessian-Affine with response
+    "hessian").  float64 arithmetic rounded once: bit-identical
     run to run and independent of the batch.  No device->host synchronisation: graph-capturable
     for fixed shapes."""
     if response not in _ops.SS_RESPONSES:
@@ -444,8 +447,38 @@ def detect_keypoints_scale_space(images, num_features=2048, response="hessian", 
         raise TypeError("detect_keypoints_scale_space: images are float32 or uint8, got %s" % images.dtype)
     if minima is None:
         minima = response == "dog"
-    return _ops.detect_scale_space(images, int(num_features), response, int(levels), float(sigma), int(min_size),
-                                   float(mr_size), bool(minima), float(k))
+    if affine and not _ops.PATCH_SIZES[0] <= int(affine_patch_size) <= _ops.PATCH_SIZES[1]:
+        raise ValueError("detect_keypoints_scale_space: affine_patch_size %r outside [8, 64]" % (affine_patch_size,))
+    lafs, scores, count = _ops.detect_scale_space(images, int(num_features), response, int(levels), float(sigma), int(min_size),
+                                                  float(mr_size), bool(minima), float(k))
+    if affine:
+        _ops.laf_affine_shape(images, lafs, count, int(affine_patch_size), out=lafs)
+    return lafs, scores, count
+
+
+def estimate_affine_shape(images, lafs, count=None, patch_size=32):
+    """Affine shape of the frames of a batch of images in one call (rr_laf_affine_shape): the
+    ``LAFAffineShapeEstimator`` of ``cirtorch/features/affine_shape.py`` -- the stage of
+    ``ScaleSpaceDetector`` between detection and orientation.
+
+    images  [B, 1|3, H, W], float32 in [0, 1] or uint8 (a pixel is v / 255); three channels are
+            reduced by 0.299 r + 0.587 g + 0.114 b
+    lafs    float32 [B, N, 2, 3] in pixels; count int32 [B] or None
+    ->      lafs float32 [B, N, 2, 3]: per frame the patch of ``make_upright(laf)`` from its pyramid
+            level (`patch_size` a side), the second-moment matrix of its Gaussian-weighted Sobel
+            gradients, ``ellipse_to_laf`` of it, rescaled to the scale of the input frame; the centre
+            is the input's.  A patch without structure (two of the three raw moments below 1e-10,
+            judged before the normalisation) keeps a circle.  Slots at or past count, slots whose
+            centre is (-1, -1) and frames with a non-finite entry hold zeros.
+
+    The result is upright; ``describe_keypoints(lafs=..., orientation=True, pyramid=True)`` gives it
+    an orientation.  float64 arithmetic rounded once: bit-identical run to run and independent of
+    the batch.  No patch is written to memory and nothing waits for the host: graph-capturable for
+    fixed shapes.  No gradients."""
+    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] not in (1, 3):
+        raise ValueError("estimate_affine_shape: images are [B, 1, H, W] or [B, 3, H, W], got %s"
+                         % (tuple(images.shape) if torch.is_tensor(images) else type(images),))
+    return _ops.laf_affine_shape(images, lafs, count, int(patch_size))
 
 
 def describe_keypoints(images, kpts, count=None, scale=12.0, lafs=None, orientation=False, patch_size=32, num_ang_bins=8,

@@ -50,6 +50,13 @@
 //
 // Bin sums by fixed lanes instead of atomics are what makes a descriptor a function of its patch
 // alone: not of the batch, the slot, the launch or the run.
+//
+// Affine shape (PatchAffineShapeEstimator.forward and LAFAffineShapeEstimator.forward of
+// cirtorch/features/affine_shape.py:36-69,91-119, ellipse_to_laf of laf.py:137-177), below the
+// describer's kernels and on its helpers: the moments of the Gaussian-weighted Sobel gradients of a
+// patch, summed by lane-owned pixels and block_sum; the degenerate rule on the raw moments, then the
+// normalisation; the closed-form inverse of the ellipse's square root; and k_laf_shape, one block per
+// frame from the upright frame's pyramid patch (LDS) to the rescaled frame.
 #include "rr_internal.h"
 
 #include <math.h>
@@ -550,8 +557,155 @@ __global__ void __launch_bounds__(Q_TB) k_describe(const void* __restrict__ x, i
     sift_phase(L, a, dst);
 }
 
+// ---- affine shape (PatchAffineShapeEstimator, ellipse_to_laf, LAFAffineShapeEstimator)
+// The block's LDS of the shape kernels: 832 bytes of tables and the patch (4 ps^2: 16 KiB at ps 64).
+struct ShapeLds {
+    double* scratch;   // [64] the unnormalised 1-D Gaussian
+    double* red;       // [8]  wave sums of a block reduction
+    float* g1;         // [64] 1-D Gaussian
+    float* patch;      // [ps ps]
+};
+
+__host__ __device__ inline size_t shape_lds_bytes(int ps) { return (64 + 8) * 8 + 64 * 4 + (size_t)ps * ps * 4; }
+
+__device__ __forceinline__ ShapeLds shape_carve(unsigned char* base) {
+    ShapeLds L;
+    L.scratch = reinterpret_cast<double*>(base);
+    L.red = L.scratch + 64;
+    L.g1 = reinterpret_cast<float*>(L.red + 8);
+    L.patch = L.g1 + 64;
+    return L;
+}
+
+// g1 of sift_phase, by its expressions in its order (the same bits): the window of both is
+// get_gaussian_kernel2d((ps, ps), (sigma, sigma), True), sigma = ps / sqrt 2
+__device__ __forceinline__ void gauss_table(const ShapeLds& L, int ps) {
+    const int tid = threadIdx.x;
+    if (tid < ps) {
+        const double x = (double)(tid - ps / 2) + ((ps & 1) ? 0.0 : 0.5);
+        L.scratch[tid] = exp(-(x * x) / ((double)ps * (double)ps));   // 2 sigma^2 = ps^2
+    }
+    __syncthreads();
+    if (tid < ps) {
+        double s = 0.0;
+        for (int i = 0; i < ps; ++i) s += L.scratch[i];
+        L.g1[tid] = (float)(L.scratch[tid] / s);
+    }
+    __syncthreads();
+}
+
+// The normalised second-moment matrix (a, b, c) of L.patch, float32, returned to every thread.
+// Lane t owns the pixels t, t + 256, ... and adds their gx^2, gx gy, gy^2 in ascending order; the 256
+// sums are combined by block_sum: a butterfly over the wave, the four waves ascending.
+__device__ void shape_phase(const ShapeLds& L, int ps, double eps, float& fa, float& fb, float& fc) {
+    const int n = ps * ps;
+    double sa = 0.0, sb = 0.0, sc = 0.0;
+    for (int i = threadIdx.x; i < n; i += Q_TB) {
+        const int y = i / ps, x = i - y * ps;
+        const int y0 = qclampi(y - 1, ps - 1) * ps, y1 = y * ps, y2 = qclampi(y + 1, ps - 1) * ps;
+        const int x0 = qclampi(x - 1, ps - 1), x2 = qclampi(x + 1, ps - 1);
+        const double a00 = L.patch[y0 + x0], a01 = L.patch[y0 + x], a02 = L.patch[y0 + x2];
+        const double a10 = L.patch[y1 + x0], a12 = L.patch[y1 + x2];
+        const double a20 = L.patch[y2 + x0], a21 = L.patch[y2 + x], a22 = L.patch[y2 + x2];
+        const double dx = ((a02 - a00) + 2.0 * (a12 - a10) + (a22 - a20)) * 0.125;
+        const double dy = ((a20 - a00) + 2.0 * (a21 - a01) + (a22 - a02)) * 0.125;
+        const double g = (double)(L.g1[y] * L.g1[x]);
+        const double gx = dx * g, gy = dy * g;   // the weight on the gradients: squared in the moments
+        sa += gx * gx;
+        sb += gx * gy;
+        sc += gy * gy;
+    }
+    double a = block_sum(sa, L.red) / (double)n;
+    double b = block_sum(sb, L.red) / (double)n;
+    double c = block_sum(sc, L.red) / (double)n;
+    if ((a < eps) + (b < eps) + (c < eps) >= 2) { a = 1.0; b = 0.0; c = 1.0; }   // before the normalisation
+    double m = a;
+    if (b > m || b != b) m = b;
+    if (c > m || c != c) m = c;
+    fa = (float)(a / m);
+    fb = (float)(b / m);
+    fc = (float)(c / m);
+}
+
+// ellipse (x, y, a, b, c) -> frame o[6]
+__device__ __forceinline__ void q_ellipse(float x, float y, float a, float b, float c, float* o) {
+    const double a11 = sqrt(fabs((double)a)), a22 = sqrt(fabs((double)c));
+    const double d = a11 + a22;
+    const double a21 = (double)b / (d < 1e-9 ? 1e-9 : d);
+    o[0] = (float)(1.0 / a11);
+    o[1] = 0.f;
+    o[2] = x;
+    o[3] = (float)(0.0 - a21 / (a11 * a22));
+    o[4] = (float)(1.0 / a22);
+    o[5] = y;
+}
+
+__device__ __forceinline__ double q_scale(double a00, double a01, double a10, double a11) {
+    return sqrt(fabs((a00 * a11 - a10 * a01) + 1e-10));
+}
+
+__global__ void __launch_bounds__(Q_TB) k_patch_shape(const float* __restrict__ patches, int ps, double eps, float* __restrict__ out) {
+    const ShapeLds L = shape_carve(q_lds);
+    const float* src = patches + (long long)blockIdx.x * ps * ps;
+    for (int i = threadIdx.x; i < ps * ps; i += Q_TB) L.patch[i] = src[i];
+    gauss_table(L, ps);
+    float a, b, c;
+    shape_phase(L, ps, eps, a, b, c);
+    if (threadIdx.x == 0) {
+        float* o = out + (long long)blockIdx.x * 3;
+        o[0] = a; o[1] = b; o[2] = c;
+    }
+}
+
+__global__ void __launch_bounds__(Q_TB) k_ellipse_to_laf(const float* __restrict__ ells, long long B, float* __restrict__ lafs) {
+    const long long i = (long long)blockIdx.x * Q_TB + threadIdx.x;
+    if (i >= B) return;
+    const float* e = ells + i * 5;
+    float o[6];
+    q_ellipse(e[0], e[1], e[2], e[3], e[4], o);
+    for (int k = 0; k < 6; ++k) lafs[i * 6 + k] = o[k];
+}
+
+// one block per keypoint slot: upright frame -> its pyramid patch (LDS) -> shape -> ellipse frame of
+// the input frame's scale.  lafs_out may be lafs: a block reads its own frame before it writes it.
+template <bool U8>
+__global__ void __launch_bounds__(Q_TB) k_laf_shape(const void* __restrict__ x, int c, int h, int w, const float* lafs,
+                                                    const int* __restrict__ count, int npts, int ps, double eps, float* lafs_out,
+                                                    const float* __restrict__ pyr, int n, int last) {
+    const int tid = threadIdx.x;
+    const long long slot = blockIdx.x, img = slot / npts;
+    const int pt = (int)(slot - img * npts);
+    const float* fp = lafs + slot * 6;
+    const Frame f{fp[0], fp[1], fp[2], fp[3], fp[4], fp[5]};
+    if ((count && pt >= count[img]) || (f.a02 == -1.f && f.a12 == -1.f) || !f.finite()) {   // block-uniform
+        __syncthreads();   // every thread has read the frame (lafs_out may be lafs)
+        if (tid < 6) lafs_out[slot * 6 + tid] = 0.f;
+        return;
+    }
+    const ShapeLds L = shape_carve(q_lds);
+    const long long hw = (long long)h * w;
+    const void* src = U8 ? (const void*)(reinterpret_cast<const unsigned char*>(x) + img * c * hw)
+                         : (const void*)(reinterpret_cast<const float*>(x) + img * c * hw);
+    double u00, u10, u11;
+    q_upright(f, u00, u10, u11);
+    const Frame u{(float)u00, 0.f, f.a02, (float)u10, (float)u11, f.a12};
+    q_patch<U8>(L.patch, src, hw, h, w, c == 3, pyr, n, img, last, u, ps);
+    gauss_table(L, ps);
+    float a, b, cc;
+    shape_phase(L, ps, eps, a, b, cc);   // its barriers are also between the reads of lafs and the write below
+    if (tid == 0) {
+        float e[6];
+        q_ellipse(f.a02, f.a12, a, b, cc, e);
+        const double s0 = q_scale(f.a00, f.a01, f.a10, f.a11), s1 = q_scale(e[0], e[1], e[3], e[4]);
+        const double r = s0 / s1;
+        float* o = lafs_out + slot * 6;
+        o[0] = (float)((double)e[0] * r); o[1] = (float)((double)e[1] * r); o[2] = f.a02;
+        o[3] = (float)((double)e[3] * r); o[4] = (float)((double)e[4] * r); o[5] = f.a12;
+    }
+}
+
 // ---------------------------------------------------------------- host
-constexpr size_t Q_WS = 256;   // no patch, gradient or plane lives in memory: the workspace is a formality
+constexpr size_t Q_WS = 256;  // no patch, gradient or plane lives in memory: the workspace is a formality
 
 bool q_pixels_ok(long long a, long long b, long long c, long long d) {
     long long p = 1;
@@ -844,6 +998,63 @@ int rr_extract_patches_pyramid(const void* x, int n, int c, int h, int w, int u8
                                npts, ps, out, levels_out, beyond_flag);
     }
     return check_launch("rr_extract_patches_pyramid");
+}
+
+int rr_patch_affine_shape(const float* patches, long long B, int ps, double eps, float* out, void* stream) {
+    const std::string nm("rr_patch_affine_shape");
+    if (B < 0 || B > Q_MAXBLOCKS) return fail(RR_EINVAL, nm + ": patch count outside [0, 2^24)");
+    if (ps < Q_MINPS || ps > Q_MAXPS) return fail(RR_EINVAL, nm + ": patch size outside [8, 64]");
+    if (!std::isfinite(eps)) return fail(RR_EINVAL, nm + ": eps must be finite");
+    if (B > 0 && (!patches || !out)) return fail(RR_EINVAL, nm + ": null input or output");
+    if (B == 0) return RR_OK;
+    hipLaunchKernelGGL(k_patch_shape, dim3((unsigned)B), dim3(Q_TB), shape_lds_bytes(ps), as_stream(stream), patches, ps, eps, out);
+    return check_launch("rr_patch_affine_shape");
+}
+
+int rr_ellipse_to_laf(const float* ells, long long B, float* lafs, void* stream) {
+    const std::string nm("rr_ellipse_to_laf");
+    if (B < 0 || B > Q_MAXBLOCKS) return fail(RR_EINVAL, nm + ": ellipse count outside [0, 2^24)");
+    if (B > 0 && (!ells || !lafs)) return fail(RR_EINVAL, nm + ": null input or output");
+    if (B == 0) return RR_OK;
+    hipLaunchKernelGGL(k_ellipse_to_laf, dim3((unsigned)((B + Q_TB - 1) / Q_TB)), dim3(Q_TB), 0, as_stream(stream), ells, B, lafs);
+    return check_launch("rr_ellipse_to_laf");
+}
+
+size_t rr_laf_affine_shape_workspace_bytes(int n, int c, int h, int w, int npts, int ps) {
+    (void)c; (void)npts;
+    int last = 0;
+    return Q_WS + align256(pyramid_bytes(n, 1, h, w, ps, last));
+}
+
+int rr_laf_affine_shape(const void* x, int n, int c, int h, int w, int u8, const float* lafs, const int* count, int npts, int ps,
+                        double eps, float* lafs_out, void* workspace, size_t workspace_bytes, void* stream) {
+    const std::string nm("rr_laf_affine_shape");
+    if (c != 1 && c != 3) return fail(RR_EINVAL, nm + ": c must be 1 or 3");
+    int rc = check_image(nm, x, n, c, h, w);
+    if (rc) return rc;
+    if (npts < 0) return fail(RR_EINVAL, nm + ": negative npts");
+    if (ps < Q_MINPS || ps > Q_MAXPS) return fail(RR_EINVAL, nm + ": patch size outside [8, 64]");
+    if (!std::isfinite(eps)) return fail(RR_EINVAL, nm + ": eps must be finite");
+    const long long blocks = (long long)n * npts;
+    if (blocks > Q_MAXBLOCKS) return fail(RR_EINVAL, nm + ": more than 2^24 - 1 keypoint slots");
+    if (blocks > 0 && (!lafs || !lafs_out)) return fail(RR_EINVAL, nm + ": null frames or output");
+    int last = 0;
+    const size_t pyr_bytes = pyramid_bytes(n, 1, h, w, ps, last);
+    if (!workspace || workspace_bytes < Q_WS + align256(pyr_bytes)) return fail(RR_ENOSPACE, nm + ": workspace too small");
+    if (blocks == 0) return RR_OK;
+    float* pyr = reinterpret_cast<float*>(workspace);
+    if (last > 0) {
+        rc = build_pyramid(nm, x, n, c, h, w, u8 != 0, c == 3, last, pyr, as_stream(stream));
+        if (rc) return rc;
+    }
+    const size_t lds = shape_lds_bytes(ps);
+    if (u8)
+        hipLaunchKernelGGL(k_laf_shape<true>, dim3((unsigned)blocks), dim3(Q_TB), lds, as_stream(stream), x, c, h, w, lafs, count,
+                           npts, ps, eps, lafs_out, pyr, n, last);
+    else
+        hipLaunchKernelGGL(k_laf_shape<false>, dim3((unsigned)blocks), dim3(Q_TB), lds, as_stream(stream), x, c, h, w, lafs, count,
+                           npts, ps, eps, lafs_out, pyr, n, last);
+    return check_launch("rr_laf_affine_shape");
 }
 
 }  // extern "C"

@@ -787,6 +787,60 @@ int rr_describe_keypoints_pyramid(const void* x, int n, int c, int h, int w, int
                                   int num_ang_bins, int num_spatial_bins, int rootsift, double clipval, float* desc,
                                   float* angles, float* lafs_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Affine shape (rr_describe.hip): the second-moment matrix of a patch's gradients, the frame of an
+ * ellipse, and the two fused per keypoint -- the stage of ScaleSpaceDetector between detection and
+ * orientation (cirtorch/features/affine_shape.py, whose kornia helpers are laf.py's).  The rules of
+ * the describe entries hold: float64 in one fixed order per output, rounded once to float32, no
+ * atomic on a floating-point value, a result depends on its own patch or frame and image only,
+ * argument errors before anything is enqueued, nothing is read back (graph-capturable), one block of
+ * 256 threads per patch or slot (rr_ellipse_to_laf: per 256 ellipses), at most 2^24 - 1 patches,
+ * ellipses or slots, 8 <= ps <= 64.
+ *
+ * rr_patch_affine_shape replaces PatchAffineShapeEstimator.forward (affine_shape.py:36-69).
+ * patches [B][ps][ps] float32, out [B][3] float32 = (a, b, c).  Per pixel, on clamped patch
+ * coordinates, dx and dy are the Sobel pair / 8 of rr_patch_orientation and
+ *   gx = dx G(y, x),  gy = dy G(y, x)
+ * with G the float32-valued window of rr_sift_describe (get_gaussian_kernel2d((ps, ps), (sigma,
+ * sigma), True), sigma = ps / sqrt 2: the same table).  The weight is on the gradients, so it enters
+ * the moments squared, as in the reference.
+ *   a = mean(gx^2),  b = mean(gx gy),  c = mean(gy^2)
+ * Each sum: thread t of the 256 adds its pixels t, t + 256, ... (row-major) in ascending order; the
+ * 256 partial sums are added by an xor butterfly over each wave of 64 (offsets 32, 16, ..., 1) and
+ * the four wave sums as ((w0 + w1) + w2) + w3; then / ps^2.  The degenerate rule comes BEFORE the
+ * normalisation: if [a < eps] + [b < eps] + [c < eps] >= 2 (a negative b counts) the shape is
+ * (1, 0, 1).  Then (a, b, c) / max(a, b, c).  The reference's default eps is 1e-10; G is of order
+ * 1 / ps^2, so raw moments of a [0, 1] image at ps 32 are 1e-9 .. 1e-7 and the threshold is live.
+ * Errors: null pointers, a bad ps, a non-finite eps, B outside [0, 2^24).  B == 0 returns RR_OK.
+ *
+ * rr_ellipse_to_laf replaces ellipse_to_laf (cirtorch/features/laf.py:137-167).  ells [B][5] float32
+ * = (x, y, a, b, c), lafs [B][2][3] float32:
+ *   a11 = sqrt|a|,  a22 = sqrt|c|,  a21 = b / max(a11 + a22, 1e-9)
+ *   lafs = [[1 / a11, 0, x], [0 - a21 / (a11 a22), 1 / a22, y]]
+ * the closed form of the reference's inverse of [[a11, 0], [a21, a22]].
+ * Errors: null pointers, B outside [0, 2^24).  B == 0 returns RR_OK.
+ *
+ * rr_laf_affine_shape replaces LAFAffineShapeEstimator.forward (affine_shape.py:91-119) by the
+ * pyramid build and one kernel, one block per slot, the patch in LDS: no patch, gradient or ellipse
+ * exists in memory.  x, count, lafs [n][npts][2][3] and the workspace
+ * (rr_laf_affine_shape_workspace_bytes; the gray pyramid at its start) are those of
+ * rr_describe_keypoints_pyramid.  Per slot: U = make_upright(frame) in float64 rounded to float32;
+ * the patch of U from U's level by the rule of rr_extract_patches_pyramid (a frame past the last
+ * level from the last level: the reference's zero patch would give a circle there), rounded to
+ * float32; (a, b, c) by rr_patch_affine_shape, rounded to float32; E = rr_ellipse_to_laf(x, y, a, b,
+ * c), rounded to float32; s0 = sqrt|det + 1e-10| of the INPUT frame's 2 x 2 part and s1 of E's; the
+ * output's 2 x 2 part is E (s0 / s1) and its centre the input's, bit for bit.  Slots at or past
+ * count[i], slots whose centre is (-1, -1) and frames with a non-finite entry get an all-zero frame.
+ * lafs_out [n][npts][2][3] may be lafs.  The result is bit-identical to rr_patch_pyramid ->
+ * rr_extract_patches_pyramid on the upright frames -> rr_patch_affine_shape -> rr_ellipse_to_laf ->
+ * that rescaling in float64.
+ * Errors: those of the entries above, c not 1 or 3, a non-finite eps, more than 2^24 - 1 slots, a
+ * short workspace (RR_ENOSPACE).  n npts == 0 returns RR_OK. */
+int rr_patch_affine_shape(const float* patches, long long B, int ps, double eps, float* out, void* stream);
+int rr_ellipse_to_laf(const float* ells, long long B, float* lafs, void* stream);
+size_t rr_laf_affine_shape_workspace_bytes(int n, int c, int h, int w, int npts, int ps);
+int rr_laf_affine_shape(const void* x, int n, int c, int h, int w, int u8, const float* lafs, const int* count, int npts, int ps,
+                        double eps, float* lafs_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Full ranking for any database size: out_idx[q][r] = the r-th database row of
  * query q by (float64 score desc, index asc) — np.argsort(-np.dot(vecs.T, qvecs),
  * axis=0) of scripts/test.py:247-248 as [nq][n] (rr_knn_topk ranks k <= 8192).
