@@ -18,6 +18,11 @@ def _st():
     return E.stream_ptr()
 
 
+def _workspace(nbytes, device):
+    """A workspace of the size the library asked for (never empty: an entry rejects a null pointer)."""
+    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+
+
 # ---------------------------------------------------------------- extractor ops
 def image_to_nhwc(img, c_pad, dtype, mean=None, std=None):
     """img: [N, C<=4, H, W] float32 (GPU) -> [N, H, W, c_pad] `dtype`, normalised
@@ -469,7 +474,7 @@ def whitenapply_rows(x, m, P, d_out):
         P = torch.nn.functional.pad(P, (0, pad))
         dim += pad
     y = torch.empty((rows, d_out), dtype=torch.float32, device=x.device)
-    ws = torch.empty(max(1, int(E.lib().rr_whiten_workspace_bytes(rows, d_out))), dtype=torch.uint8, device=x.device)
+    ws = _workspace(E.lib().rr_whiten_workspace_bytes(rows, d_out), x.device)
     E.check(E.lib().rr_whitenapply(E.ptr(x), rows, dim, E.ptr(m), E.ptr(P), int(d_out), E.ptr(y), E.ptr(ws),
                                    ws.numel(), _st()), "rr_whitenapply")
     return y
@@ -499,7 +504,7 @@ def knn_topk(db, db_f32, q, q_f32, k, cand=0, idx_offset=0, workspace=None, db_n
     nq = q.shape[0]
     need = knn_workspace_bytes(n_db, nq, d, k, cand, db.dtype)
     if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=db.device)
+        workspace = _workspace(need, db.device)
     out_s = torch.empty((nq, k), dtype=torch.float64, device=db.device)
     out_i = torch.empty((nq, k), dtype=torch.int64, device=db.device)
     if db_norm_max is None:
@@ -532,7 +537,7 @@ def rank_full(db_f32, q_f32):
     assert db_f32.is_contiguous() and q_f32.is_contiguous() and db_f32.shape[1] == q_f32.shape[1]
     n, d = db_f32.shape
     nq = q_f32.shape[0]
-    ws = torch.empty(int(E.lib().rr_rank_workspace_bytes(n, nq)), dtype=torch.uint8, device=db_f32.device)
+    ws = _workspace(E.lib().rr_rank_workspace_bytes(n, nq), db_f32.device)
     out = torch.empty((nq, n), dtype=torch.int64, device=db_f32.device)
     E.check(E.lib().rr_rank_full(E.ptr(db_f32), n, E.ptr(q_f32), nq, d, E.ptr(out), E.ptr(ws), ws.numel(), _st()),
             "rr_rank_full")
@@ -629,7 +634,7 @@ def local_head(x, kpts, weight, bias):
     b = bias.contiguous().float() if bias is not None else None
     e = wt.shape[0]
     out = torch.empty((n, npts, e), dtype=torch.float32, device=x.device)
-    ws = torch.empty(int(E.lib().rr_local_head_workspace_bytes(n * npts, c, e)), dtype=torch.uint8, device=x.device)
+    ws = _workspace(E.lib().rr_local_head_workspace_bytes(n * npts, c, e), x.device)
     E.check(E.lib().rr_local_head(E.ptr(xh), n, h, w, c, E.dtype_code(xh.dtype), E.ptr(kp), npts, E.ptr(wt), E.ptr(b),
                                   e, E.ptr(out), E.ptr(ws), ws.numel(), _st()), "rr_local_head")
     return out
@@ -672,7 +677,7 @@ def match_top2(a, a_off, b, b_off, max_n1=None, max_n2=None):
     d21 = torch.full((rows2, 2), float("inf"), dtype=torch.float64, device=dev)
     i12 = torch.full((rows1, 2), -1, dtype=torch.int32, device=dev)
     i21 = torch.full((rows2, 2), -1, dtype=torch.int32, device=dev)
-    ws = torch.empty(int(E.lib().rr_match_workspace_bytes(rows1, rows2, 0)), dtype=torch.uint8, device=dev)
+    ws = _workspace(E.lib().rr_match_workspace_bytes(rows1, rows2, 0), dev)
     E.check(E.lib().rr_match_top2(E.ptr(a), E.ptr(a_off), rows1, E.ptr(b), E.ptr(b_off), rows2, npairs, d, max_n1,
                                   max_n2, E.ptr(d12), E.ptr(i12), E.ptr(d21), E.ptr(i21), E.ptr(ws), ws.numel(),
                                   _st()), "rr_match_top2")
@@ -693,7 +698,7 @@ def match_pairs(a, a_off, b, b_off, mode, th=0.8, max_n1=None, max_n2=None, cove
     else:
         match = torch.full((rows1,), -1, dtype=torch.int64, device=dev)
         dist = torch.full((rows1,), float("inf"), dtype=torch.float32, device=dev)
-    ws = torch.empty(int(E.lib().rr_match_workspace_bytes(rows1, rows2, 1)), dtype=torch.uint8, device=dev)
+    ws = _workspace(E.lib().rr_match_workspace_bytes(rows1, rows2, 1), dev)
     E.check(E.lib().rr_match_pairs(E.ptr(a), E.ptr(a_off), rows1, E.ptr(b), E.ptr(b_off), rows2, npairs, d, max_n1,
                                    max_n2, MATCH_MODES[mode], float(th), E.ptr(match), E.ptr(dist), E.ptr(ws),
                                    ws.numel(), _st()), "rr_match_pairs")
@@ -721,7 +726,7 @@ def verify_pairs(kp1, off1, kp2, off2, match, th=3.0, iters=1024, refine=2, seed
     inliers = torch.empty(npairs, dtype=torch.int32, device=dev)   # written for every pair
     H = torch.empty((npairs, 3, 3), dtype=torch.float64, device=dev)
     mask = (torch.empty if covered and npairs else torch.zeros)(rows1, dtype=torch.uint8, device=dev)
-    ws = torch.empty(int(E.lib().rr_verify_workspace_bytes(rows1, npairs, int(iters))), dtype=torch.uint8, device=dev)
+    ws = _workspace(E.lib().rr_verify_workspace_bytes(rows1, npairs, int(iters)), dev)
     E.check(E.lib().rr_verify_pairs(E.ptr(kp1), E.ptr(off1), rows1, E.ptr(kp2), E.ptr(off2), rows2, E.ptr(match),
                                     npairs, max_n1, float(th), int(iters), int(refine),
                                     int(seed) & 0xFFFFFFFFFFFFFFFF, E.ptr(inliers), E.ptr(H), E.ptr(mask), E.ptr(ws),
@@ -829,7 +834,7 @@ def select_keypoints(score, num, ks=5, min_score=0.0, border=0):
     kpts = torch.empty((n, num, 2), dtype=torch.float32, device=dev)
     scores = torch.empty((n, num), dtype=torch.float32, device=dev)
     count = torch.empty(n, dtype=torch.int32, device=dev)
-    ws = torch.empty(int(E.lib().rr_detect_workspace_bytes(n, h, w, int(num))), dtype=torch.uint8, device=dev)
+    ws = _workspace(E.lib().rr_detect_workspace_bytes(n, h, w, int(num)), dev)
     E.check(E.lib().rr_select_keypoints(E.ptr(score), n, h, w, int(ks), int(num), float(min_score), int(border),
                                         E.ptr(kpts), E.ptr(scores), E.ptr(count), E.ptr(ws), ws.numel(), _st()),
             "rr_select_keypoints")
@@ -852,7 +857,7 @@ def detect_keypoints(x, num, kind="harris", k=0.04, ks=5, min_score=0.0, border=
     scores = torch.empty((n, num), dtype=torch.float32, device=dev)
     count = torch.empty(n, dtype=torch.int32, device=dev)
     smap = torch.empty((n, 1, h, w), dtype=torch.float32, device=dev) if return_response else None
-    ws = torch.empty(int(E.lib().rr_detect_workspace_bytes(n, h, w, int(num))), dtype=torch.uint8, device=dev)
+    ws = _workspace(E.lib().rr_detect_workspace_bytes(n, h, w, int(num)), dev)
     E.check(E.lib().rr_detect_keypoints(E.ptr(x), n, c, h, w, int(x.dtype == torch.uint8), RESPONSES[kind], float(k),
                                         E.ptr(sg), int(ks), int(num), float(min_score), int(border), E.ptr(kpts),
                                         E.ptr(scores), E.ptr(count), E.ptr(smap), E.ptr(ws), ws.numel(), _st()),
@@ -936,7 +941,7 @@ def scale_pyramid(x, levels=3, sigma=1.6, min_size=15):
     args = (int(levels), float(sigma), int(min_size))
     E.check(E.lib().rr_scale_pyramid_bytes(n, c, h, w, *args, ctypes.byref(ob), ctypes.byref(wb)), "rr_scale_pyramid_bytes")
     out = torch.empty(ob.value // 4, dtype=torch.float32, device=x.device)
-    ws = torch.empty(wb.value, dtype=torch.uint8, device=x.device)
+    ws = _workspace(wb.value, x.device)
     E.check(E.lib().rr_scale_pyramid(E.ptr(x), n, c, h, w, int(x.dtype == torch.uint8), *args, E.ptr(out), ob.value,
                                      E.ptr(ws), ws.numel(), _st()), "rr_scale_pyramid")
     octs = pyramid_plan(n, h, w, *args)
@@ -996,7 +1001,7 @@ def scale_space_select(resp, n, h, w, num, levels=3, sigma=1.6, min_size=15, min
     if resp.dtype != torch.float32 or resp.dim() != 1 or resp.numel() < need["off"] + n * (args[0] + 3) * need["h"] * need["w"]:
         raise RuntimeError("scale_space_select: resp must be the flat float32 buffer of the pyramid's layout")
     lafs, scores, count = _ss_outputs(n, int(num), resp.device)
-    ws = torch.empty(int(E.lib().rr_detect_scale_space_workspace_bytes(n, 1, h, w, *args)), dtype=torch.uint8, device=resp.device)
+    ws = _workspace(E.lib().rr_detect_scale_space_workspace_bytes(n, 1, h, w, *args), resp.device)
     E.check(E.lib().rr_scale_space_select(E.ptr(resp), n, h, w, *args, int(bool(minima)), float(mr_size), int(num), E.ptr(lafs),
                                           E.ptr(scores), E.ptr(count), E.ptr(ws), ws.numel(), _st()), "rr_scale_space_select")
     return lafs, scores, count
@@ -1014,11 +1019,10 @@ def detect_scale_space(x, num, kind="hessian", levels=3, sigma=1.6, min_size=15,
     n, c, h, w = x.shape
     args = (int(levels), float(sigma), int(min_size))
     lafs, scores, count = _ss_outputs(n, int(num), x.device)
-    nbytes = int(E.lib().rr_detect_scale_space_workspace_bytes(n, c, h, w, *args))
-    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=x.device)
+    ws = _workspace(E.lib().rr_detect_scale_space_workspace_bytes(n, c, h, w, *args), x.device)
     E.check(E.lib().rr_detect_scale_space(E.ptr(x), n, c, h, w, int(x.dtype == torch.uint8), *args, SS_RESPONSES[kind],
                                           float(k), int(bool(minima)), float(mr_size), int(num), E.ptr(lafs), E.ptr(scores),
-                                          E.ptr(count), E.ptr(ws), nbytes, _st()), "rr_detect_scale_space")
+                                          E.ptr(count), E.ptr(ws), ws.numel(), _st()), "rr_detect_scale_space")
     if not return_pyramid:
         return lafs, scores, count
     pad = (-ws.data_ptr()) % 256
@@ -1241,13 +1245,13 @@ def describe_keypoints(x, kpts=None, count=None, scale=12.0, lafs=None, orient=F
     angles = torch.empty((n, npts), dtype=torch.float32, device=dev)
     lafs_out = torch.empty((n, npts, 2, 3), dtype=torch.float32, device=dev) if return_lafs else None
     if pyramid:
-        ws = torch.empty(int(E.lib().rr_describe_pyramid_workspace_bytes(n, c, h, w, npts, ps, nb, ns)), dtype=torch.uint8, device=dev)
+        ws = _workspace(E.lib().rr_describe_pyramid_workspace_bytes(n, c, h, w, npts, ps, nb, ns), dev)
         E.check(E.lib().rr_describe_keypoints_pyramid(E.ptr(x), n, c, h, w, int(x.dtype == torch.uint8), E.ptr(kpts), E.ptr(count),
                                                       npts, float(scale), E.ptr(lafs), int(bool(orient)), int(orient_bins), ps, nb,
                                                       ns, int(bool(rootsift)), float(clipval), E.ptr(desc), E.ptr(angles),
                                                       E.ptr(lafs_out), E.ptr(ws), ws.numel(), _st()), "rr_describe_keypoints_pyramid")
         return (desc, angles, lafs_out) if return_lafs else (desc, angles)
-    ws = torch.empty(int(E.lib().rr_describe_workspace_bytes(n, npts, ps, nb, ns)), dtype=torch.uint8, device=dev)
+    ws = _workspace(E.lib().rr_describe_workspace_bytes(n, npts, ps, nb, ns), dev)
     E.check(E.lib().rr_describe_keypoints(E.ptr(x), n, c, h, w, int(x.dtype == torch.uint8), E.ptr(kpts), E.ptr(count), npts,
                                           float(scale), E.ptr(lafs), int(bool(orient)), int(orient_bins), ps, nb, ns,
                                           int(bool(rootsift)), float(clipval), E.ptr(desc), E.ptr(angles), E.ptr(lafs_out),
@@ -1308,7 +1312,7 @@ def laf_affine_shape(x, lafs, count=None, ps=32, eps=1e-10, out=None):
         out = torch.empty((n, npts, 2, 3), dtype=torch.float32, device=x.device)
     elif out.dtype != torch.float32 or tuple(out.shape) != (n, npts, 2, 3) or not out.is_contiguous():
         raise ValueError("laf_affine_shape: out must be contiguous float32 [%d, %d, 2, 3]" % (n, npts))
-    ws = torch.empty(int(E.lib().rr_laf_affine_shape_workspace_bytes(n, c, h, w, npts, ps)), dtype=torch.uint8, device=x.device)
+    ws = _workspace(E.lib().rr_laf_affine_shape_workspace_bytes(n, c, h, w, npts, ps), x.device)
     E.check(E.lib().rr_laf_affine_shape(E.ptr(x), n, c, h, w, int(x.dtype == torch.uint8), E.ptr(lafs), E.ptr(count), npts, ps,
                                         float(eps), E.ptr(out), E.ptr(ws), ws.numel(), _st()), "rr_laf_affine_shape")
     return out

@@ -58,6 +58,7 @@
 // normalisation; the closed-form inverse of the ellipse's square root; and k_laf_shape, one block per
 // frame from the upright frame's pyramid patch (LDS) to the rescaled frame.
 #include "rr_internal.h"
+#include "rr_workspace.h"
 
 #include <math.h>
 
@@ -74,8 +75,6 @@ constexpr int Q_MAXOBINS = 64;                // orientation bins
 constexpr long long Q_MAXPIX = 1ll << 31;
 constexpr long long Q_MAXBLOCKS = (1ll << 24) - 1;   // one block of 256 threads each: a grid holds fewer than 2^32 threads
 constexpr double Q_PI = (double)3.14159265358979323846f;   // the float32 value, as the reference's pi tensor
-
-__device__ __forceinline__ int qclampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 template <bool U8> __device__ __forceinline__ double q_load(const void* x, long long i) {
     if constexpr (U8)  // IEEE division: the same float as torch's x.float() / 255
@@ -154,10 +153,6 @@ __device__ __forceinline__ int q_patch(float* __restrict__ dst, const void* src0
     return lv;
 }
 
-__device__ __forceinline__ int qreflecti(int v, int size) {   // reflect without the edge sample, then clamped
-    return qclampi(v < 0 ? -v : (v >= size ? 2 * size - 2 - v : v), size - 1);
-}
-
 constexpr int P_T = 32, P_TY = 16;       // output tile: 32 wide, 16 tall (28 KiB of LDS: five blocks per CU)
 constexpr int P_IN = 2 * P_T + 4;       // input tile with its halo: 68 columns
 constexpr int P_INY = 2 * P_TY + 4;     // and 36 rows
@@ -181,7 +176,7 @@ __global__ void __launch_bounds__(Q_TB) k_pyrdown(const void* __restrict__ x, in
     for (int i = tid; i < P_INY * P_IN; i += Q_TB) {
         const int ly = i / P_IN, r = i - ly * P_IN;
         const int odd = r >= P_HALF, lx = 2 * (r - odd * P_HALF) + odd;
-        const long long o = base + (long long)qreflecti(2 * oy0 - 2 + ly, h) * w + qreflecti(2 * ox0 - 2 + lx, w);
+        const long long o = base + (long long)reflect_clampi(2 * oy0 - 2 + ly, h) * w + reflect_clampi(2 * ox0 - 2 + lx, w);
         tile[i] = q_pixel<U8>(x, hw, o, gray);
     }
     __syncthreads();
@@ -281,8 +276,8 @@ __device__ float orient_phase(const Lds& L, int ps, int nb) {
     const int tid = threadIdx.x, n = ps * ps;
     for (int i = tid; i < n; i += Q_TB) {
         const int y = i / ps, x = i - y * ps;
-        const int y0 = qclampi(y - 1, ps - 1) * ps, y1 = y * ps, y2 = qclampi(y + 1, ps - 1) * ps;
-        const int x0 = qclampi(x - 1, ps - 1), x2 = qclampi(x + 1, ps - 1);
+        const int y0 = clampi(y - 1, ps - 1) * ps, y1 = y * ps, y2 = clampi(y + 1, ps - 1) * ps;
+        const int x0 = clampi(x - 1, ps - 1), x2 = clampi(x + 1, ps - 1);
         const double a00 = L.patch[y0 + x0], a01 = L.patch[y0 + x], a02 = L.patch[y0 + x2];
         const double a10 = L.patch[y1 + x0], a12 = L.patch[y1 + x2];
         const double a20 = L.patch[y2 + x0], a21 = L.patch[y2 + x], a22 = L.patch[y2 + x2];
@@ -355,8 +350,8 @@ __device__ void sift_phase(const Lds& L, const SiftArgs& a, float* __restrict__ 
     __syncthreads();
     for (int i = tid; i < n; i += Q_TB) {
         const int y = i / ps, x = i - y * ps;
-        const double gx = ((double)L.patch[y * ps + qclampi(x + 1, ps - 1)] - (double)L.patch[y * ps + qclampi(x - 1, ps - 1)]) * 0.5;
-        const double gy = ((double)L.patch[qclampi(y + 1, ps - 1) * ps + x] - (double)L.patch[qclampi(y - 1, ps - 1) * ps + x]) * 0.5;
+        const double gx = ((double)L.patch[y * ps + clampi(x + 1, ps - 1)] - (double)L.patch[y * ps + clampi(x - 1, ps - 1)]) * 0.5;
+        const double gy = ((double)L.patch[clampi(y + 1, ps - 1) * ps + x] - (double)L.patch[clampi(y - 1, ps - 1) * ps + x]) * 0.5;
         const double mag = sqrt((gx * gx + gy * gy) + 1e-10) * (double)(L.g1[y] * L.g1[x]);
         const double ori = atan2(gy, gx + 1e-10) + 2.0 * Q_PI;
         soft_bin(((double)nb * ori) / (2.0 * Q_PI), mag, nb, i, L);
@@ -602,8 +597,8 @@ __device__ void shape_phase(const ShapeLds& L, int ps, double eps, float& fa, fl
     double sa = 0.0, sb = 0.0, sc = 0.0;
     for (int i = threadIdx.x; i < n; i += Q_TB) {
         const int y = i / ps, x = i - y * ps;
-        const int y0 = qclampi(y - 1, ps - 1) * ps, y1 = y * ps, y2 = qclampi(y + 1, ps - 1) * ps;
-        const int x0 = qclampi(x - 1, ps - 1), x2 = qclampi(x + 1, ps - 1);
+        const int y0 = clampi(y - 1, ps - 1) * ps, y1 = y * ps, y2 = clampi(y + 1, ps - 1) * ps;
+        const int x0 = clampi(x - 1, ps - 1), x2 = clampi(x + 1, ps - 1);
         const double a00 = L.patch[y0 + x0], a01 = L.patch[y0 + x], a02 = L.patch[y0 + x2];
         const double a10 = L.patch[y1 + x0], a12 = L.patch[y1 + x2];
         const double a20 = L.patch[y2 + x0], a21 = L.patch[y2 + x], a22 = L.patch[y2 + x2];
@@ -705,8 +700,6 @@ __global__ void __launch_bounds__(Q_TB) k_laf_shape(const void* __restrict__ x, 
 }
 
 // ---------------------------------------------------------------- host
-constexpr size_t Q_WS = 256;  // no patch, gradient or plane lives in memory: the workspace is a formality
-
 bool q_pixels_ok(long long a, long long b, long long c, long long d) {
     long long p = 1;
     for (long long f : {a, b, c, d}) {
@@ -756,8 +749,6 @@ template <typename K> int want_lds(K kernel, size_t bytes, const std::string& w)
     return RR_OK;
 }
 
-size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-
 // bytes of levels 1 .. last of n c planes of h x w (level l is (h >> l) x (w >> l): floor(h / 2) repeated),
 // last = the largest l with min(h_l, w_l) >= ps, 0 when there is none or an argument is out of range
 size_t pyramid_bytes(int n, int c, int h, int w, int ps, int& last) {
@@ -800,6 +791,19 @@ int build_pyramid(const std::string& nm, const void* x, int n, int c, int h, int
     return RR_OK;
 }
 
+// the describe entries and rr_laf_affine_shape: no patch, gradient or plane lives in memory, only
+// (pyramid) the gray levels 1 .. last, first in the workspace
+struct DescribeWs {
+    float* pyr;
+    int last;
+};
+
+DescribeWs layout(Arena& a, bool pyramid, int n, int h, int w, int ps) {
+    int last = 0;
+    const size_t bytes = pyramid ? pyramid_bytes(n, 1, h, w, ps, last) : 0;
+    return {a.take<float>(bytes / sizeof(float)), last};
+}
+
 }  // namespace
 
 }  // namespace rr
@@ -809,8 +813,8 @@ using namespace rr;
 extern "C" {
 
 size_t rr_describe_workspace_bytes(int n, int npts, int ps, int num_ang_bins, int num_spatial_bins) {
-    (void)n; (void)npts; (void)ps; (void)num_ang_bins; (void)num_spatial_bins;
-    return Q_WS;
+    (void)npts; (void)num_ang_bins; (void)num_spatial_bins;
+    return measured(layout, false, n, 0, 0, ps);
 }
 
 int rr_extract_patches(const void* x, int n, int c, int h, int w, int u8, int gray, const float* lafs, int npts, int ps,
@@ -883,13 +887,12 @@ static int describe(const std::string& nm, bool pyramid, const void* x, int n, i
     const long long blocks = (long long)n * npts;
     if (blocks > Q_MAXBLOCKS) return fail(RR_EINVAL, nm + ": more than 2^24 - 1 keypoint slots");
     if (blocks > 0 && ((!kpts && !lafs) || !desc)) return fail(RR_EINVAL, nm + ": null keypoints or output");
-    int last = 0;
-    const size_t pyr_bytes = pyramid ? pyramid_bytes(n, 1, h, w, ps, last) : 0;
-    if (!workspace || workspace_bytes < Q_WS + align256(pyr_bytes)) return fail(RR_ENOSPACE, nm + ": workspace too small");
+    Arena arena(workspace, workspace_bytes);
+    const auto [pyr, last] = layout(arena, pyramid, n, h, w, ps);
+    if (!workspace || !arena.fits()) return fail(RR_ENOSPACE, nm + ": workspace too small");
     if (blocks == 0) return RR_OK;
-    const float* pyr = reinterpret_cast<const float*>(workspace);
-    if (pyramid && last > 0) {
-        rc = build_pyramid(nm, x, n, c, h, w, u8 != 0, c == 3, last, reinterpret_cast<float*>(workspace), as_stream(stream));
+    if (last > 0) {
+        rc = build_pyramid(nm, x, n, c, h, w, u8 != 0, c == 3, last, pyr, as_stream(stream));
         if (rc) return rc;
     }
     const size_t lds = lds_bytes(ps, a.nb * a.ns * a.ns, a.ksize);
@@ -920,8 +923,7 @@ int rr_describe_keypoints(const void* x, int n, int c, int h, int w, int u8, con
 
 size_t rr_describe_pyramid_workspace_bytes(int n, int c, int h, int w, int npts, int ps, int num_ang_bins, int num_spatial_bins) {
     (void)c; (void)npts; (void)num_ang_bins; (void)num_spatial_bins;
-    int last = 0;
-    return Q_WS + align256(pyramid_bytes(n, 1, h, w, ps, last));
+    return measured(layout, true, n, h, w, ps);
 }
 
 int rr_describe_keypoints_pyramid(const void* x, int n, int c, int h, int w, int u8, const float* kpts, const int* count,
@@ -1022,8 +1024,7 @@ int rr_ellipse_to_laf(const float* ells, long long B, float* lafs, void* stream)
 
 size_t rr_laf_affine_shape_workspace_bytes(int n, int c, int h, int w, int npts, int ps) {
     (void)c; (void)npts;
-    int last = 0;
-    return Q_WS + align256(pyramid_bytes(n, 1, h, w, ps, last));
+    return measured(layout, true, n, h, w, ps);
 }
 
 int rr_laf_affine_shape(const void* x, int n, int c, int h, int w, int u8, const float* lafs, const int* count, int npts, int ps,
@@ -1038,11 +1039,10 @@ int rr_laf_affine_shape(const void* x, int n, int c, int h, int w, int u8, const
     const long long blocks = (long long)n * npts;
     if (blocks > Q_MAXBLOCKS) return fail(RR_EINVAL, nm + ": more than 2^24 - 1 keypoint slots");
     if (blocks > 0 && (!lafs || !lafs_out)) return fail(RR_EINVAL, nm + ": null frames or output");
-    int last = 0;
-    const size_t pyr_bytes = pyramid_bytes(n, 1, h, w, ps, last);
-    if (!workspace || workspace_bytes < Q_WS + align256(pyr_bytes)) return fail(RR_ENOSPACE, nm + ": workspace too small");
+    Arena arena(workspace, workspace_bytes);
+    const auto [pyr, last] = layout(arena, true, n, h, w, ps);
+    if (!workspace || !arena.fits()) return fail(RR_ENOSPACE, nm + ": workspace too small");
     if (blocks == 0) return RR_OK;
-    float* pyr = reinterpret_cast<float*>(workspace);
     if (last > 0) {
         rc = build_pyramid(nm, x, n, c, h, w, u8 != 0, c == 3, last, pyr, as_stream(stream));
         if (rc) return rc;

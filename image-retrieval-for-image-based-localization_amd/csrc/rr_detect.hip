@@ -54,6 +54,7 @@
 // of its window only: not on n, the tile, the launch or the run.
 #include "rr_internal.h"
 #include "rr_select.h"
+#include "rr_workspace.h"
 
 #include <math.h>
 
@@ -77,7 +78,6 @@ __device__ const double D_GW[7] = {0x1.228634p-8, 0x1.ba69e8p-5, 0x1.efb0bp-3, 0
 __device__ const double D_GXX[5][5] = {{-1, 0, 2, 0, -1}, {-4, 0, 8, 0, -4}, {-6, 0, 12, 0, -6}, {-4, 0, 8, 0, -4}, {-1, 0, 2, 0, -1}};
 __device__ const double D_GXY[5][5] = {{-1, -2, 0, 2, 1}, {-2, -4, 0, 4, 2}, {0, 0, 0, 0, 0}, {2, 4, 0, -4, -2}, {1, 2, 0, -2, -1}};
 
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 // reflect padding without the edge sample; |overshoot| <= 3 < size
 __device__ __forceinline__ int reflecti(int v, int size) { return v < 0 ? -v : (v >= size ? 2 * size - 2 - v : v); }
 
@@ -272,10 +272,6 @@ __global__ void __launch_bounds__(256) k_nms(const float* __restrict__ x, int h,
     }
 }
 
-__global__ void __launch_bounds__(256) k_reset_counts(int* __restrict__ cnt, int n) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) cnt[i] = 0;
-}
 
 // One block per tile of an image.  No two 8-neighbours are both kept, so a tile holds at most
 // D_CW D_CH / 4 candidates: they are collected in LDS and appended with ONE global atomic per block
@@ -346,16 +342,19 @@ __global__ void __launch_bounds__(D_SEL_TB) k_select(const unsigned long long* _
 }
 
 // ---------------------------------------------------------------- host
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 long long cand_cap(int h, int w) { return (long long)((h + 1) / 2) * ((w + 1) / 2); }
 
-size_t map_bytes(int n, int h, int w) { return align256((size_t)n * h * w * 4); }
+struct DetectWs {
+    float* map;                  // the score map of rr_detect_keypoints without score_map
+    unsigned long long* keys;    // cand_cap candidate keys per image
+    int* cnt;
+};
 
-size_t ws_bytes(int n, int h, int w, int num) {
-    (void)num;   // the selected keys live in LDS
-    if (n <= 0 || h <= 0 || w <= 0) return 256;
-    return map_bytes(n, h, w) + align256((size_t)n * (size_t)cand_cap(h, w) * 8) + align256((size_t)n * 4) + 256;
+// (the selected keys live in LDS: num takes no room)
+DetectWs layout(Arena& a, int n, int h, int w) {
+    if (n <= 0 || h <= 0 || w <= 0) return {};
+    return {a.take<float>((size_t)n * h * w), a.take<unsigned long long>((size_t)n * (size_t)cand_cap(h, w)),
+            a.take<int>((size_t)n)};
 }
 
 // a b c d <= 2^31 without overflow (all factors >= 0)
@@ -406,22 +405,18 @@ int check_select(const std::string& w, int n, int h, int wd, int ks, int num, fl
 }
 
 int launch_select(const float* score, int n, int h, int w, int ks, int num, float min_score, int border, float* kpts,
-                  float* scores, int* count, void* workspace, hipStream_t s, const char* what) {
-    char* q = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    q += map_bytes(n, h, w);
+                  float* scores, int* count, const DetectWs& ws, hipStream_t s, const char* what) {
     const long long cap = cand_cap(h, w);
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(q); q += align256((size_t)n * (size_t)cap * 8);
-    int* cnt = reinterpret_cast<int*>(q);
     // the counters are reset by a kernel, not hipMemsetAsync (captured memset nodes: DESIGN.md §4, kNN)
-    hipLaunchKernelGGL(k_reset_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, cnt, n);
+    hipLaunchKernelGGL(k_reset_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws.cnt, n);
     int rc = check_launch(what);
     if (rc) return rc;
     const unsigned tiles_x = (unsigned)((w + D_CW - 1) / D_CW), tiles = tiles_x * (unsigned)((h + D_CH - 1) / D_CH);
     hipLaunchKernelGGL(k_candidates, dim3((unsigned)n * tiles), dim3(256), 0, s, score, h, w, ks / 2, min_score, border, cap,
-                       tiles_x, tiles, keys, cnt);
+                       tiles_x, tiles, ws.keys, ws.cnt);
     rc = check_launch(what);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_select, dim3((unsigned)n), dim3(D_SEL_TB), 0, s, keys, cnt, cap, w, num, kpts, scores, count);
+    hipLaunchKernelGGL(k_select, dim3((unsigned)n), dim3(D_SEL_TB), 0, s, ws.keys, ws.cnt, cap, w, num, kpts, scores, count);
     return check_launch(what);
 }
 
@@ -433,7 +428,10 @@ using namespace rr;
 
 extern "C" {
 
-size_t rr_detect_workspace_bytes(int n, int h, int w, int num) { return ws_bytes(n, h, w, num); }
+size_t rr_detect_workspace_bytes(int n, int h, int w, int num) {
+    (void)num;
+    return measured(layout, n, h, w);
+}
 
 int rr_response(const void* x, int n, int c, int h, int w, int u8, int gray, int kind, double k, const float* sigmas,
                 float* out, void* stream) {
@@ -467,9 +465,11 @@ int rr_select_keypoints(const float* score, int n, int h, int w, int ks, int num
     int rc = check_select(nm, n, h, w, ks, num, min_score, border);
     if (rc) return rc;
     if (n > 0 && (!score || !kpts || !scores || !count)) return fail(RR_EINVAL, nm + ": null input or output");
-    if (!workspace || workspace_bytes < ws_bytes(n, h, w, num)) return fail(RR_ENOSPACE, nm + ": workspace too small");
+    Arena arena(workspace, workspace_bytes);
+    const DetectWs ws = layout(arena, n, h, w);
+    if (!workspace || !arena.fits()) return fail(RR_ENOSPACE, nm + ": workspace too small");
     if (n == 0) return RR_OK;
-    return launch_select(score, n, h, w, ks, num, min_score, border, kpts, scores, count, workspace, as_stream(stream),
+    return launch_select(score, n, h, w, ks, num, min_score, border, kpts, scores, count, ws, as_stream(stream),
                          "rr_select_keypoints");
 }
 
@@ -483,13 +483,14 @@ int rr_detect_keypoints(const void* x, int n, int c, int h, int w, int u8, int k
     rc = check_select(nm, n, h, w, ks, num, min_score, border);
     if (rc) return rc;
     if (n > 0 && (!kpts || !scores || !count)) return fail(RR_EINVAL, nm + ": null output");
-    if (!workspace || workspace_bytes < ws_bytes(n, h, w, num)) return fail(RR_ENOSPACE, nm + ": workspace too small");
+    Arena arena(workspace, workspace_bytes);
+    const DetectWs ws = layout(arena, n, h, w);
+    if (!workspace || !arena.fits()) return fail(RR_ENOSPACE, nm + ": workspace too small");
     if (n == 0) return RR_OK;
-    float* map = score_map ? score_map
-                           : reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    float* map = score_map ? score_map : ws.map;
     rc = launch_response(x, n, c, h, w, u8 != 0, c == 3, kind, k, sigmas, map, as_stream(stream), "rr_detect_keypoints");
     if (rc) return rc;
-    return launch_select(map, n, h, w, ks, num, min_score, border, kpts, scores, count, workspace, as_stream(stream),
+    return launch_select(map, n, h, w, ks, num, min_score, border, kpts, scores, count, ws, as_stream(stream),
                          "rr_detect_keypoints");
 }
 

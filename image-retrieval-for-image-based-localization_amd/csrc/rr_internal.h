@@ -279,4 +279,12 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// Integer pixel addressing of rr_detect / rr_scalespace / rr_describe.  Integers only: those files
+// differ in `#pragma clang fp contract`, so a shared floating-point helper would change one side's bits.
+__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+// reflect padding without the edge sample, then clamped (coordinates past one reflection)
+__device__ __forceinline__ int reflect_clampi(int v, int size) {
+    return clampi(v < 0 ? -v : (v >= size ? 2 * size - 2 - v : v), size - 1);
+}
+
 }  // namespace rr

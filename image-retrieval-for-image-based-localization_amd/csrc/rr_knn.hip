@@ -20,6 +20,7 @@
 // KC > k is the screening margin: bf16 scores err by ~1e-4, exact-f32 by
 // ~1e-7, far below KC-k candidates' worth of score density at the boundary.
 #include "rr_internal.h"
+#include "rr_workspace.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -855,7 +856,19 @@ static int pow2_at_least(int v) {
 struct KnnPlan {
     int L, nchunks, G, KC, npow2;
     long long S;
-    size_t slab_bytes, cand_bytes, sel_bytes, fin_bytes, tau_bytes, cnt_bytes, total;  // tau_bytes: tau + sel_thr + prune_thr
+};
+
+struct KnnWs {   // in layout order
+    float* slab;
+    uint32_t* cand_k;
+    int* cand_i;
+    uint32_t* sel_k;
+    int* sel_i;
+    double* fin_s;
+    int* fin_i;
+    uint32_t *tau, *sel_thr;
+    float* prune_thr;
+    int* cnt;
 };
 
 static int default_cand(int k, int dtype) {
@@ -878,15 +891,14 @@ static KnnPlan plan(long long n_db, int nq, int k, int cand, int dtype) {
     p.G = (int)g;
     p.S = ((long long)p.G * p.L + 3) / 4 * 4;
     p.npow2 = pow2_at_least(p.KC);
-    p.slab_bytes = ((size_t)nq * p.S * 4 + 255) / 256 * 256;
-    p.cand_bytes = (size_t)nq * p.nchunks * p.KC * 4;
-    p.sel_bytes = ((size_t)nq * p.KC * 4 + 255) / 256 * 256;
-    p.fin_bytes = ((size_t)nq * p.npow2 * 8 + 255) / 256 * 256 + ((size_t)nq * p.npow2 * 4 + 255) / 256 * 256;
-    p.tau_bytes = ((size_t)nq * 12 + 255) / 256 * 256;  // tau, sel_thr, prune_thr
-    p.cnt_bytes = ((size_t)nq * p.nchunks * 4 + 255) / 256 * 256;
-    p.total = p.slab_bytes + 2 * ((p.cand_bytes + 255) / 256 * 256) + 2 * p.sel_bytes + p.fin_bytes + p.tau_bytes +
-              p.cnt_bytes;
     return p;
+}
+
+static KnnWs layout(Arena& a, const KnnPlan& p, int nq) {
+    const size_t q = (size_t)nq, cands = q * p.nchunks * p.KC, sel = q * p.KC, fin = q * p.npow2;
+    return {a.take<float>(q * p.S), a.take<uint32_t>(cands), a.take<int>(cands), a.take<uint32_t>(sel), a.take<int>(sel),
+            a.take<double>(fin), a.take<int>(fin), a.take<uint32_t>(q), a.take<uint32_t>(q), a.take<float>(q),
+            a.take<int>(q * p.nchunks)};
 }
 
 }  // namespace rr
@@ -898,7 +910,7 @@ extern "C" {
 size_t rr_knn_workspace_bytes(long long n_db, int nq, int d, int k, int cand, int dtype) {
     (void)d;
     if (n_db <= 0 || nq <= 0) return 0;
-    return plan(n_db, nq, k, cand, dtype).total;
+    return measured(layout, plan(n_db, nq, k, cand, dtype), nq);
 }
 
 static int knn_topk_impl(const void* db, const float* db_f32, long long n_db, const void* q, const float* q_f32,
@@ -928,22 +940,10 @@ static int knn_topk_impl(const void* db, const float* db_f32, long long n_db, co
     KnnPlan p = plan(n_db, nq, k, cand, dtype);
     if (p.KC < k) return fail(RR_EINVAL, "rr_knn_topk: cand must be >= k");
     if (p.npow2 > MAX_SORT) return fail(RR_EINVAL, "rr_knn_topk: k / cand too large (max 8192)");
-    if (workspace_bytes < p.total || !workspace) return fail(RR_ENOSPACE, "rr_knn_topk: workspace too small");
+    Arena arena(workspace, workspace_bytes);
+    const auto [slab, cand_k, cand_i, sel_k, sel_i, fin_s, fin_i, tau, sel_thr, prune_thr, cnt] = layout(arena, p, nq);
+    if (!workspace || !arena.fits()) return fail(RR_ENOSPACE, "rr_knn_topk: workspace too small");
     hipStream_t s = as_stream(stream);
-    char* ws = (char*)workspace;
-    float* slab = (float*)ws;
-    uint32_t* cand_k = (uint32_t*)(ws + p.slab_bytes);
-    int* cand_i = (int*)(ws + p.slab_bytes + (p.cand_bytes + 255) / 256 * 256);
-    char* fws = ws + p.slab_bytes + 2 * ((p.cand_bytes + 255) / 256 * 256);
-    uint32_t* sel_k = (uint32_t*)fws;
-    int* sel_i = (int*)(fws + p.sel_bytes);
-    double* fin_s = (double*)(fws + 2 * p.sel_bytes);
-    int* fin_i = (int*)(fws + 2 * p.sel_bytes + ((size_t)nq * p.npow2 * 8 + 255) / 256 * 256);
-    uint32_t* tau = (uint32_t*)(fws + 2 * p.sel_bytes + p.fin_bytes);
-    uint32_t* sel_thr = tau + nq;
-    float* prune_thr = reinterpret_cast<float*>(sel_thr + nq);
-    int* cnt = (int*)(fws + 2 * p.sel_bytes + p.fin_bytes + p.tau_bytes);
-
     static bool attr_done = false;
     if (!attr_done) {
         (void)hipFuncSetAttribute((const void*)k_chunk_select, hipFuncAttributeMaxDynamicSharedMemorySize, CHUNK_L * 4);
@@ -979,7 +979,7 @@ static int knn_topk_impl(const void* db, const float* db_f32, long long n_db, co
     const long long nreset = (long long)nq * p.nchunks > nq ? (long long)nq * p.nchunks : nq;
     hipLaunchKernelGGL(k_knn_reset, dim3((unsigned)((nreset + 255) / 256)), dim3(256), 0, s, tau, cnt, nq, p.nchunks, g0,
                        p.KC, tau_memset ? 0 : 1);
-    auto score_args = [&](long long r0, int rows) {
+    auto score_args = [&, slab = slab](long long r0, int rows) {   // (C++17 lambdas capture no structured binding)
         ConvArgs a{};
         a.x = q;
         a.w = (const char*)db + (size_t)r0 * d * esz;

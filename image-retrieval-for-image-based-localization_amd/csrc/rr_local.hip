@@ -14,6 +14,7 @@
 // zero padding per tap.  Linear on the exact-f32 MFMA (rr_linear_rows), then
 // x / max(||x||_2, 1e-12) per descriptor.
 #include "rr_internal.h"
+#include "rr_workspace.h"
 
 namespace rr {
 
@@ -128,6 +129,15 @@ __global__ void k_mutual(const long long* __restrict__ nn12, int n1, const long 
     match[i] = (j >= 0 && j < n2 && nn21[j] == i) ? j : -1;
 }
 
+struct LocalWs {
+    float *samp, *lin;   // sampled rows [nkp][c], linear rows [nkp][e]
+};
+
+LocalWs layout(Arena& a, long long nkp, int c, int e) {
+    const size_t rows = (size_t)(nkp > 0 ? nkp : 0);
+    return {a.take<float>(rows * (size_t)c), a.take<float>(rows * (size_t)e)};
+}
+
 }  // namespace
 
 }  // namespace rr
@@ -137,7 +147,7 @@ using namespace rr;
 extern "C" {
 
 size_t rr_local_head_workspace_bytes(long long nkp, int c, int e) {
-    return (size_t)nkp * ((size_t)c + (size_t)e) * sizeof(float) + 256;
+    return measured(layout, nkp, c, e);
 }
 
 int rr_local_head(const void* x, int n, int h, int w, int c, int dtype, const float* kpts, int npts,
@@ -150,12 +160,11 @@ int rr_local_head(const void* x, int n, int h, int w, int c, int dtype, const fl
     if (c % vec || (((uintptr_t)x) & 15)) return fail(RR_EINVAL, "rr_local_head: c must fill 16-byte lanes");
     if (c % 4) return fail(RR_EINVAL, "rr_local_head: c % 4 != 0");
     const long long nkp = (long long)n * npts;
-    if (!workspace || workspace_bytes < rr_local_head_workspace_bytes(nkp, c, e))
-        return fail(RR_ENOSPACE, "rr_local_head: workspace too small");
+    Arena arena(workspace, workspace_bytes);
+    const auto [samp, lin] = layout(arena, nkp, c, e);
+    if (!workspace || !arena.fits()) return fail(RR_ENOSPACE, "rr_local_head: workspace too small");
     if (nkp > 0x7fffffffll) return fail(RR_EINVAL, "rr_local_head: too many keypoints");
     hipStream_t s = as_stream(stream);
-    float* samp = (float*)workspace;
-    float* lin = samp + nkp * c;
     const unsigned g = (unsigned)((nkp + 3) / 4);
     if (dtype == RR_BF16)
         hipLaunchKernelGGL(k_grid_sample_nhwc<bf16_t>, dim3(g), dim3(256), 0, s, (const bf16_t*)x, h, w, c, kpts, npts,

@@ -24,6 +24,7 @@
 // a lane is a strict-< insert, and the 16 lists of a query row (4 lane groups
 // x 4 waves) are merged once at the end by (distance, index).
 #include "rr_internal.h"
+#include "rr_workspace.h"
 
 #include <math.h>
 
@@ -285,22 +286,14 @@ struct MatchWs {
     int* ii[2];
 };
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-size_t ws_bytes(long long rows1, long long rows2, int lists) {
-    const size_t r1 = (size_t)(rows1 > 0 ? rows1 : 0), r2 = (size_t)(rows2 > 0 ? rows2 : 0);
-    size_t n = align256(r1 * 8) + align256(r2 * 8);
-    if (lists) n += align256(r1 * 16) + align256(r2 * 16) + align256(r1 * 8) + align256(r2 * 8);
-    return n + 256;
-}
-
-MatchWs carve(void* workspace, long long rows1, long long rows2) {
-    char* p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    MatchWs w;
-    const size_t r[2] = {(size_t)rows1, (size_t)rows2};
-    for (int s = 0; s < 2; ++s) { w.nrm[s] = reinterpret_cast<double*>(p); p += align256(r[s] * 8); }
-    for (int s = 0; s < 2; ++s) { w.dd[s] = reinterpret_cast<double*>(p); p += align256(r[s] * 16); }
-    for (int s = 0; s < 2; ++s) { w.ii[s] = reinterpret_cast<int*>(p); p += align256(r[s] * 8); }
+// lists: the two directions' top-2 lists of rr_match_pairs; rr_match_top2 writes the caller's
+MatchWs layout(Arena& a, long long rows1, long long rows2, int lists) {
+    const size_t r[2] = {(size_t)(rows1 > 0 ? rows1 : 0), (size_t)(rows2 > 0 ? rows2 : 0)};
+    MatchWs w{};
+    for (int s = 0; s < 2; ++s) w.nrm[s] = a.take<double>(r[s]);
+    if (!lists) return w;
+    for (int s = 0; s < 2; ++s) w.dd[s] = a.take<double>(r[s] * 2);
+    for (int s = 0; s < 2; ++s) w.ii[s] = a.take<int>(r[s] * 2);
     return w;
 }
 
@@ -356,7 +349,7 @@ using namespace rr;
 
 extern "C" {
 
-size_t rr_match_workspace_bytes(long long rows1, long long rows2, int lists) { return ws_bytes(rows1, rows2, lists); }
+size_t rr_match_workspace_bytes(long long rows1, long long rows2, int lists) { return measured(layout, rows1, rows2, lists); }
 
 int rr_match_top2(const float* a, const long long* a_off, long long rows1, const float* b, const long long* b_off,
                   long long rows2, int npairs, int d, int max_n1, int max_n2, double* d12, int* i12, double* d21,
@@ -365,9 +358,10 @@ int rr_match_top2(const float* a, const long long* a_off, long long rows1, const
     if (rc) return rc;
     if ((rows1 > 0 && (!d12 || !i12)) || (rows2 > 0 && (!d21 || !i21)))
         return fail(RR_EINVAL, "rr_match_top2: null output");
-    if (!workspace || workspace_bytes < ws_bytes(rows1, rows2, 0))
+    Arena arena(workspace, workspace_bytes);
+    const MatchWs w = layout(arena, rows1, rows2, 0);
+    if (!workspace || !arena.fits())
         return fail(RR_ENOSPACE, "rr_match_top2: workspace too small");
-    const MatchWs w = carve(workspace, rows1, rows2);
     return launch_top2(a, a_off, rows1, b, b_off, rows2, npairs, d, max_n1, max_n2, d12, i12, d21, i21, w.nrm[0],
                        w.nrm[1], as_stream(stream));
 }
@@ -380,10 +374,11 @@ int rr_match_pairs(const float* a, const long long* a_off, long long rows1, cons
     if (mode != RR_MATCH_NN && mode != RR_MATCH_MNN && mode != RR_MATCH_SNN && mode != RR_MATCH_SMNN)
         return fail(RR_EINVAL, "rr_match_pairs: unknown mode");
     if (rows1 > 0 && (!match || !dist)) return fail(RR_EINVAL, "rr_match_pairs: null output");
-    if (!workspace || workspace_bytes < ws_bytes(rows1, rows2, 1))
+    Arena arena(workspace, workspace_bytes);
+    const MatchWs w = layout(arena, rows1, rows2, 1);
+    if (!workspace || !arena.fits())
         return fail(RR_ENOSPACE, "rr_match_pairs: workspace too small");
     if (npairs == 0 || max_n1 == 0) return RR_OK;
-    const MatchWs w = carve(workspace, rows1, rows2);
     hipStream_t s = as_stream(stream);
     rc = launch_top2(a, a_off, rows1, b, b_off, rows2, npairs, d, max_n1, max_n2, w.dd[0], w.ii[0], w.dd[1], w.ii[1],
                      w.nrm[0], w.nrm[1], s);

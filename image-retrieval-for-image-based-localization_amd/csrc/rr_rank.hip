@@ -20,6 +20,7 @@
 //                  scatter keeps equal keys in index order (the input is in
 //                  index order), which is the (score desc, index asc) rule.
 #include "rr_internal.h"
+#include "rr_workspace.h"
 
 #include <utility>
 
@@ -187,17 +188,23 @@ __global__ void __launch_bounds__(RT) k_radix_scatter(const unsigned long long* 
 
 struct RankPlan {
     int ntiles;
-    size_t keys_bytes, idx_bytes, hist_bytes, total;
+};
+
+struct RankWs {
+    unsigned long long *k0, *k1;
+    unsigned *i0, *i1, *hist;
 };
 
 RankPlan rank_plan(long long n, int nq) {
     RankPlan p;
     p.ntiles = (int)((n + RTILE - 1) / RTILE);
-    p.keys_bytes = ((size_t)nq * n * 8 + 255) / 256 * 256;
-    p.idx_bytes = ((size_t)nq * n * 4 + 255) / 256 * 256;
-    p.hist_bytes = ((size_t)nq * 256 * p.ntiles * 4 + 255) / 256 * 256;
-    p.total = 2 * p.keys_bytes + 2 * p.idx_bytes + p.hist_bytes;
     return p;
+}
+
+RankWs layout(Arena& a, const RankPlan& p, long long n, int nq) {
+    const size_t keys = (size_t)nq * n;
+    return {a.take<unsigned long long>(keys), a.take<unsigned long long>(keys), a.take<unsigned>(keys),
+            a.take<unsigned>(keys), a.take<unsigned>((size_t)nq * 256 * p.ntiles)};
 }
 
 }  // namespace
@@ -209,7 +216,7 @@ extern "C" {
 
 size_t rr_rank_workspace_bytes(long long n, int nq) {
     if (n <= 0 || nq <= 0) return 0;
-    return rank_plan(n, nq).total;
+    return measured(layout, rank_plan(n, nq), n, nq);
 }
 
 int rr_rank_full(const float* db_f32, long long n, const float* q_f32, int nq, int d, long long* out_idx,
@@ -219,17 +226,13 @@ int rr_rank_full(const float* db_f32, long long n, const float* q_f32, int nq, i
     if (d <= 0 || d % 256) return fail(RR_EINVAL, "rr_rank_full: d must be a multiple of 256 (zero-pad)");
     if ((size_t)RQG * d * 4 > 160 * 1024) return fail(RR_EINVAL, "rr_rank_full: d too large for the LDS query tile");
     const RankPlan p = rank_plan(n, nq);
-    if (!workspace || workspace_bytes < p.total) return fail(RR_ENOSPACE, "rr_rank_full: workspace too small");
+    Arena arena(workspace, workspace_bytes);
+    auto [k0, k1, i0, i1, hist] = layout(arena, p, n, nq);   // the passes swap k0 / k1 and i0 / i1
+    if (!workspace || !arena.fits()) return fail(RR_ENOSPACE, "rr_rank_full: workspace too small");
     if (nq > 65535) return fail(RR_EINVAL, "rr_rank_full: more than 65535 queries per call (grid y); split them");
     if ((long long)nq * p.ntiles > 0x7fffffffll)
         return fail(RR_EINVAL, "rr_rank_full: problem too large");
     hipStream_t s = as_stream(stream);
-    char* ws = (char*)workspace;
-    unsigned long long* k0 = (unsigned long long*)ws;
-    unsigned long long* k1 = (unsigned long long*)(ws + p.keys_bytes);
-    unsigned* i0 = (unsigned*)(ws + 2 * p.keys_bytes);
-    unsigned* i1 = (unsigned*)(ws + 2 * p.keys_bytes + p.idx_bytes);
-    unsigned* hist = (unsigned*)(ws + 2 * p.keys_bytes + 2 * p.idx_bytes);
     static bool attr = false;
     if (!attr) {
         (void)hipFuncSetAttribute((const void*)k_rank_scores, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

@@ -37,6 +37,7 @@
 //               score; the slots past count hold a zero frame and 0.
 #include "rr_internal.h"
 #include "rr_select.h"
+#include "rr_workspace.h"
 
 #include <math.h>
 
@@ -55,13 +56,8 @@ constexpr long long S_MAXPIX = 1ll << 31;
 
 struct Taps { float t[S_MAXK]; };
 
-__device__ __forceinline__ int sclampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-// reflect padding without the edge sample (|overshoot| < size for every coordinate an in-map output
-// reads); coordinates that only outputs outside the map read are clamped
-__device__ __forceinline__ int sreflecti(int v, int size) {
-    return sclampi(v < 0 ? -v : (v >= size ? 2 * size - 2 - v : v), size - 1);
-}
-
+// reflect_clampi: |overshoot| < size for every coordinate an in-map output reads; coordinates that
+// only outputs outside the map read are clamped
 // IN: 0 float32, 1 uint8 (/ 255 in IEEE float32), 2 float64
 template <int IN> __device__ __forceinline__ double load_in(const void* x, long long i) {
     if constexpr (IN == 1)
@@ -88,7 +84,7 @@ __global__ void __launch_bounds__(S_TB) k_blur(const void* __restrict__ x, int h
 
     for (int i = tid; i < side * side; i += S_TB) {
         const int ly = i / side, lx = i - ly * side;
-        const long long o = src + (long long)sreflecti(ty0 - p + ly, h) * w + sreflecti(tx0 - p + lx, w);
+        const long long o = src + (long long)reflect_clampi(ty0 - p + ly, h) * w + reflect_clampi(tx0 - p + lx, w);
         double v;
         if (gray)
             v = (0.299 * load_in<IN>(x, o) + 0.587 * load_in<IN>(x, hw + o)) + 0.114 * load_in<IN>(x, 2 * hw + o);
@@ -357,14 +353,8 @@ __global__ void __launch_bounds__(D_SEL_TB) k_ss_select(const unsigned long long
     if (tid == 0) count[b] = want;
 }
 
-__global__ void __launch_bounds__(S_TB) k_ss_reset(int* __restrict__ cnt, int n) {
-    const int i = blockIdx.x * S_TB + threadIdx.x;
-    if (i < n) cnt[i] = 0;
-}
 
 // ---------------------------------------------------------------- host
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-char* align_ptr(void* p) { return reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(p) + 255) & ~(uintptr_t)255); }
 
 // the float32 values of get_gaussian_kernel1d(ks, sigma): each exp in float64, the sum ascending, the
 // quotient rounded to float32
@@ -488,14 +478,21 @@ int make_plan(const std::string& nm, int n, int c, int h, int w, int levels, dou
     return RR_OK;
 }
 
-size_t pyr_out_bytes(const Plan& P) { return align256((size_t)P.total * 4); }
-size_t pyr_ws_bytes(int n, int h, int w) { return 3 * align256((size_t)n * h * w * 8) + 256; }
+// the caller's output buffer of rr_scale_pyramid
+size_t pyr_out_bytes(const Plan& P) { return ((size_t)P.total * 4 + 255) / 256 * 256; }
 
-int launch_pyramid(const void* x, int n, int c, int h, int w, int u8, const Plan& P, float* out, void* workspace,
+struct PyrWs {
+    double* buf[3];   // working planes [n][h][w]
+};
+
+PyrWs pyr_layout(Arena& a, int n, int h, int w) {
+    const size_t plane = (size_t)n * h * w;
+    return {{a.take<double>(plane), a.take<double>(plane), a.take<double>(plane)}};
+}
+
+int launch_pyramid(const void* x, int n, int c, int h, int w, int u8, const Plan& P, float* out, const PyrWs& ws,
                    hipStream_t s, const char* what) {
-    char* q = align_ptr(workspace);
-    double* buf[3];
-    for (int i = 0; i < 3; ++i) { buf[i] = reinterpret_cast<double*>(q); q += align256((size_t)n * h * w * 8); }
+    double* const* buf = ws.buf;
     int rot = 0;   // level l of the current octave lives in buf[(rot + l) % 3]
     // the float32 levels of an octave are [n][L][h][w] (plane stride L h w per image), the working planes [n][h][w]
     int rc = launch_blur(x, u8 ? 1 : 0, c == 3, n, h, w, P.ks0 ? P.ks0 : 1, P.ks0 ? P.s0 : 1.0, (long long)P.L * h * w,
@@ -530,12 +527,26 @@ long long cand_cap(const Plan& P) {
     return c;
 }
 
-size_t select_ws_bytes(int n, const Plan& P) { return align256((size_t)n * (size_t)cand_cap(P) * 8) + align256((size_t)n * 4) + 256; }
+struct SelectWs {
+    unsigned long long* keys;   // cand_cap candidate keys per image
+    int* cnt;
+};
 
-size_t detect_ws_bytes(int n, int h, int w, const Plan& P) {
-    // pyramid, working planes, sigmas, responses, keys and counters
-    return pyr_out_bytes(P) + 256 + pyr_ws_bytes(n, h, w) + align256((size_t)n * P.L * 4) + pyr_out_bytes(P) + 256 +
-           select_ws_bytes(n, P);
+SelectWs select_layout(Arena& a, int n, const Plan& P) {
+    return {a.take<unsigned long long>((size_t)n * (size_t)cand_cap(P)), a.take<int>((size_t)n)};
+}
+
+struct DetectWs {
+    float* pyr;    // first: _ops.detect_scale_space(return_pyramid=True) reads it at the aligned start
+    PyrWs pw;
+    float* sig;
+    float* resp;   // the pyramid's layout
+    SelectWs sel;
+};
+
+DetectWs detect_layout(Arena& a, int n, int h, int w, const Plan& P) {
+    return {a.take<float>((size_t)P.total), pyr_layout(a, n, h, w), a.take<float>((size_t)n * P.L),
+            a.take<float>((size_t)P.total), select_layout(a, n, P)};
 }
 
 int check_select(const std::string& nm, int n, const Plan& P, int minima, double mr, int num) {
@@ -550,12 +561,9 @@ int check_select(const std::string& nm, int n, const Plan& P, int minima, double
 
 // resp: the pyramid's layout; the first L - 1 planes of every image and octave are the volume
 int launch_select(const float* resp, int n, int H, int W, const Plan& P, int levels, int minima, double mr, int num,
-                  float* lafs, float* scores, int* count, void* workspace, hipStream_t s, const char* what) {
-    char* q = align_ptr(workspace);
+                  float* lafs, float* scores, int* count, const SelectWs& ws, hipStream_t s, const char* what) {
     const long long cap = cand_cap(P);
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(q); q += align256((size_t)n * (size_t)cap * 8);
-    int* cnt = reinterpret_cast<int*>(q);
-    hipLaunchKernelGGL(k_ss_reset, dim3((unsigned)((n + S_TB - 1) / S_TB)), dim3(S_TB), 0, s, cnt, n);
+    hipLaunchKernelGGL(k_reset_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws.cnt, n);
     int rc = check_launch(what);
     if (rc) return rc;
     SelTab tab;
@@ -569,12 +577,12 @@ int launch_select(const float* resp, int n, int H, int W, const Plan& P, int lev
         const unsigned bpi = (unsigned)((vol + S_TB - 1) / S_TB);
         if ((long long)bpi * n > 0x7fffffffll) return fail(RR_EINVAL, std::string(what) + ": more than 2^31 - 1 blocks");
         hipLaunchKernelGGL(k_ss_candidates, dim3(bpi * (unsigned)n), dim3(S_TB), 0, s, resp + o.off, (long long)P.L * hw, D, o.h,
-                           o.w, minima, o.first_sigma, levels, mr, base, bpi, cap, keys, cnt);
+                           o.w, minima, o.first_sigma, levels, mr, base, bpi, cap, ws.keys, ws.cnt);
         rc = check_launch(what);
         if (rc) return rc;
         base += (uint32_t)vol;
     }
-    hipLaunchKernelGGL(k_ss_select, dim3((unsigned)n), dim3(D_SEL_TB), 0, s, keys, cnt, cap, tab, levels, mr, H, W, num, lafs,
+    hipLaunchKernelGGL(k_ss_select, dim3((unsigned)n), dim3(D_SEL_TB), 0, s, ws.keys, ws.cnt, cap, tab, levels, mr, H, W, num, lafs,
                        scores, count);
     return check_launch(what);
 }
@@ -602,7 +610,7 @@ int rr_scale_pyramid_bytes(int n, int c, int h, int w, int levels, double sigma,
     int rc = make_plan("rr_scale_pyramid_bytes", n, c, h, w, levels, sigma, min_size, P);
     if (rc) return rc;
     if (out_bytes) *out_bytes = pyr_out_bytes(P);
-    if (workspace_bytes) *workspace_bytes = pyr_ws_bytes(n, h, w);
+    if (workspace_bytes) *workspace_bytes = measured(pyr_layout, n, h, w);
     return RR_OK;
 }
 
@@ -614,9 +622,11 @@ int rr_scale_pyramid(const void* x, int n, int c, int h, int w, int u8, int leve
     if (rc) return rc;
     if (n > 0 && (!x || !out)) return fail(RR_EINVAL, nm + ": null input or output");
     if (out_bytes < pyr_out_bytes(P)) return fail(RR_ENOSPACE, nm + ": output buffer too small");
-    if (!workspace || workspace_bytes < pyr_ws_bytes(n, h, w)) return fail(RR_ENOSPACE, nm + ": workspace too small");
+    Arena arena(workspace, workspace_bytes);
+    const PyrWs ws = pyr_layout(arena, n, h, w);
+    if (!workspace || !arena.fits()) return fail(RR_ENOSPACE, nm + ": workspace too small");
     if (n == 0) return RR_OK;
-    return launch_pyramid(x, n, c, h, w, u8 != 0, P, out, workspace, as_stream(stream), "rr_scale_pyramid");
+    return launch_pyramid(x, n, c, h, w, u8 != 0, P, out, ws, as_stream(stream), "rr_scale_pyramid");
 }
 
 int rr_dog_response(const float* levels, int n, int L, int h, int w, float* out, void* stream) {
@@ -650,7 +660,7 @@ int rr_scale_space_extrema(const float* x, int n, int D, int h, int w, int minim
 size_t rr_detect_scale_space_workspace_bytes(int n, int c, int h, int w, int levels, double sigma, int min_size) {
     Plan P;
     if (make_plan("rr_detect_scale_space_workspace_bytes", n, c, h, w, levels, sigma, min_size, P)) return 0;
-    return detect_ws_bytes(n, h, w, P);
+    return measured(detect_layout, n, h, w, P);
 }
 
 int rr_scale_space_select(const float* resp, int n, int h, int w, int levels, double sigma, int min_size, int minima,
@@ -663,9 +673,11 @@ int rr_scale_space_select(const float* resp, int n, int h, int w, int levels, do
     rc = check_select(nm, n, P, minima, mr_size, num);
     if (rc) return rc;
     if (n > 0 && (!resp || !lafs || !scores || !count)) return fail(RR_EINVAL, nm + ": null input or output");
-    if (!workspace || workspace_bytes < select_ws_bytes(n, P)) return fail(RR_ENOSPACE, nm + ": workspace too small");
+    Arena arena(workspace, workspace_bytes);
+    const SelectWs ws = select_layout(arena, n, P);
+    if (!workspace || !arena.fits()) return fail(RR_ENOSPACE, nm + ": workspace too small");
     if (n == 0) return RR_OK;
-    return launch_select(resp, n, h, w, P, levels, minima, mr_size, num, lafs, scores, count, workspace, as_stream(stream),
+    return launch_select(resp, n, h, w, P, levels, minima, mr_size, num, lafs, scores, count, ws, as_stream(stream),
                          "rr_scale_space_select");
 }
 
@@ -685,16 +697,12 @@ int rr_detect_scale_space(const void* x, int n, int c, int h, int w, int u8, int
     rc = check_select(nm, n, P, minima, mr_size, num);
     if (rc) return rc;
     if (n > 0 && (!x || !lafs || !scores || !count)) return fail(RR_EINVAL, nm + ": null input or output");
-    if (!workspace || workspace_bytes < detect_ws_bytes(n, h, w, P)) return fail(RR_ENOSPACE, nm + ": workspace too small");
+    Arena arena(workspace, workspace_bytes);
+    const auto [pyr, pw, sig, resp, sel] = detect_layout(arena, n, h, w, P);
+    if (!workspace || !arena.fits()) return fail(RR_ENOSPACE, nm + ": workspace too small");
     if (n == 0) return RR_OK;
     hipStream_t s = as_stream(stream);
-    char* q = align_ptr(workspace);
-    float* pyr = reinterpret_cast<float*>(q); q += pyr_out_bytes(P);
-    void* pws = q; q += pyr_ws_bytes(n, h, w);
-    q = align_ptr(q);
-    float* sig = reinterpret_cast<float*>(q); q += align256((size_t)n * P.L * 4);
-    float* resp = reinterpret_cast<float*>(q); q += pyr_out_bytes(P);
-    rc = launch_pyramid(x, n, c, h, w, u8 != 0, P, pyr, pws, s, "rr_detect_scale_space");
+    rc = launch_pyramid(x, n, c, h, w, u8 != 0, P, pyr, pw, s, "rr_detect_scale_space");
     if (rc) return rc;
     for (int i = 0; i < P.n_oct; ++i) {
         const OctPlan& o = P.o[i];
@@ -714,7 +722,7 @@ int rr_detect_scale_space(const void* x, int n, int c, int h, int w, int u8, int
         }
         if (rc) return rc;
     }
-    return launch_select(resp, n, h, w, P, levels, minima, mr_size, num, lafs, scores, count, q, s, "rr_detect_scale_space");
+    return launch_select(resp, n, h, w, P, levels, minima, mr_size, num, lafs, scores, count, sel, s, "rr_detect_scale_space");
 }
 
 }  // extern "C"

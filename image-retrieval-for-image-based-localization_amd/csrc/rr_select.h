@@ -1,5 +1,6 @@
 // The best `num` of a list of unique 64-bit keys, sorted descending, by one block of D_SEL_TB threads:
-// shared by k_select (rr_detect.hip) and k_ss_select (rr_scalespace.hip).
+// shared by k_select (rr_detect.hip) and k_ss_select (rr_scalespace.hip), with the reset of the
+// per-image candidate counters that both run first.
 #pragma once
 
 #include "rr_internal.h"
@@ -11,6 +12,11 @@ constexpr int D_MAXNUM = 8192;     // keypoints per image (64 KiB of keys in LDS
 
 __device__ __forceinline__ float key_score(uint32_t k) {
     return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
+}
+
+static __global__ void __launch_bounds__(256) k_reset_counts(int* __restrict__ cnt, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) cnt[i] = 0;
 }
 
 struct SelLds {

@@ -42,6 +42,7 @@
 // A result depends on nothing but the pair's own data, seed, p and t: not on npairs, the grid or
 // which pairs share the launch (the block size of every kernel is the constant 256).
 #include "rr_internal.h"
+#include "rr_workspace.h"
 
 #include <math.h>
 
@@ -623,14 +624,18 @@ __global__ void __launch_bounds__(V_TB, 3) k_dlt_batch(const double* __restrict_
 }
 
 // ---------------------------------------------------------------- host
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 int chunks_of(int iters) { return (iters + V_TB - 1) / V_TB; }
 
-size_t ws_bytes(long long rows1, int npairs, int iters) {
+struct VerifyWs {
+    double* rec;               // 4 per side-1 row
+    int* cnt;                  // per pair
+    unsigned long long* best;  // per (pair, chunk)
+};
+
+VerifyWs layout(Arena& a, long long rows1, int npairs, int iters) {
     const size_t r1 = (size_t)(rows1 > 0 ? rows1 : 0), np = (size_t)(npairs > 0 ? npairs : 0);
     const size_t ch = (size_t)(iters > 0 ? chunks_of(iters) : 1);
-    return align256(r1 * 32) + align256(np * 4) + align256(np * ch * 8) + 256;
+    return {a.take<double>(r1 * 4), a.take<int>(np), a.take<unsigned long long>(np * ch)};
 }
 
 }  // namespace
@@ -641,7 +646,7 @@ using namespace rr;
 
 extern "C" {
 
-size_t rr_verify_workspace_bytes(long long rows1, int npairs, int iters) { return ws_bytes(rows1, npairs, iters); }
+size_t rr_verify_workspace_bytes(long long rows1, int npairs, int iters) { return measured(layout, rows1, npairs, iters); }
 
 int rr_verify_pairs(const float* kp1, const long long* off1, long long rows1, const float* kp2, const long long* off2,
                     long long rows2, const long long* match, int npairs, int max_n1, double th, int iters, int refine,
@@ -660,13 +665,10 @@ int rr_verify_pairs(const float* kp1, const long long* off1, long long rows1, co
     if (rows1 > 0x7fffffffll || rows2 > 0x7fffffffll) return fail(RR_EINVAL, w + ": too many rows");
     if (npairs > 0 && (rows1 > 0 && !mask)) return fail(RR_EINVAL, w + ": null output");
     if (npairs > 0 && (!inliers || !H)) return fail(RR_EINVAL, w + ": null output");
-    if (!workspace || workspace_bytes < ws_bytes(rows1, npairs, iters))
-        return fail(RR_ENOSPACE, w + ": workspace too small");
+    Arena arena(workspace, workspace_bytes);
+    const auto [rec, cnt, best] = layout(arena, rows1, npairs, iters);
+    if (!workspace || !arena.fits()) return fail(RR_ENOSPACE, w + ": workspace too small");
     if (npairs == 0) return RR_OK;
-    char* q = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    double* rec = reinterpret_cast<double*>(q); q += align256((size_t)rows1 * 32);
-    int* cnt = reinterpret_cast<int*>(q); q += align256((size_t)npairs * 4);
-    unsigned long long* best = reinterpret_cast<unsigned long long*>(q);
     hipStream_t s = as_stream(stream);
     const int chunks = chunks_of(iters);
     const unsigned gp = (unsigned)(npairs < 65535 ? npairs : 65535);

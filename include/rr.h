@@ -11,7 +11,9 @@
  *   - every function returns 0 on success, a negative code on error;
  *     rr_last_error() returns the message (thread-local).
  *   - all tensor pointers are DEVICE pointers; nothing here allocates:
- *     scratch is caller-provided and sized by the matching *_workspace_bytes.
+ *     scratch is caller-provided and sized by the matching *_workspace_bytes
+ *     (a workspace may start at any address: its blocks begin at the next
+ *     256-byte boundary, and the size includes that slack).
  *   - `stream` is a hipStream_t (NULL = default stream); every call only
  *     enqueues work (no host synchronisation), so calls are graph-capturable.
  *   - activations are NHWC ("channels_last"); dtype codes below.
@@ -770,7 +772,7 @@ int rr_describe_keypoints(const void* x, int n, int c, int h, int w, int u8, con
  * when last_level is 0.
  *
  * rr_describe_keypoints_pyramid takes the arguments of rr_describe_keypoints, builds the gray
- * pyramid at the start of the workspace (rr_describe_pyramid_workspace_bytes) and describes; every
+ * pyramid at the (256-byte aligned) start of the workspace (rr_describe_pyramid_workspace_bytes) and describes; every
  * patch, the upright frame's and the described frame's, comes from the level of the frame it is
  * sampled from.  desc is bit-identical to rr_patch_pyramid -> rr_extract_patches_pyramid on lafs_out
  * -> rr_sift_describe, theta to rr_patch_orientation on the pyramid patches of the upright frames,
@@ -822,7 +824,7 @@ int rr_describe_keypoints_pyramid(const void* x, int n, int c, int h, int w, int
  * rr_laf_affine_shape replaces LAFAffineShapeEstimator.forward (affine_shape.py:91-119) by the
  * pyramid build and one kernel, one block per slot, the patch in LDS: no patch, gradient or ellipse
  * exists in memory.  x, count, lafs [n][npts][2][3] and the workspace
- * (rr_laf_affine_shape_workspace_bytes; the gray pyramid at its start) are those of
+ * (rr_laf_affine_shape_workspace_bytes; the gray pyramid at its 256-byte aligned start) are those of
  * rr_describe_keypoints_pyramid.  Per slot: U = make_upright(frame) in float64 rounded to float32;
  * the patch of U from U's level by the rule of rr_extract_patches_pyramid (a frame past the last
  * level from the last level: the reference's zero patch would give a circle there), rounded to

@@ -15,6 +15,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../../image-retrieval-for-image-based-localization_amd/csrc/rr_workspace.h"
 #include "../../include/rr.h"
 
 static int g_fail = 0;
@@ -30,8 +31,58 @@ static int g_fail = 0;
 // a non-null, never-dereferenced stand-in for a device address
 static void* fake(size_t off = 0) { return reinterpret_cast<void*>(static_cast<uintptr_t>(0x100000000ull + off)); }
 
+// the blocks of one arena pass: mixed element sizes, a zero-length and a 1-byte block
+struct ArenaBlocks {
+    char* p[6];
+    size_t len[6];
+};
+
+static ArenaBlocks arena_blocks(rr::Arena& a) {
+    ArenaBlocks b{};
+    const size_t cnt[6] = {300, 0, 1, 77, 1000, 5};
+    b.p[0] = (char*)a.take<float>(cnt[0]);     b.len[0] = cnt[0] * 4;
+    b.p[1] = (char*)a.take<double>(cnt[1]);    b.len[1] = 0;
+    b.p[2] = (char*)a.take<char>(cnt[2]);      b.len[2] = 1;
+    b.p[3] = (char*)a.take<double>(cnt[3]);    b.len[3] = cnt[3] * 8;
+    b.p[4] = (char*)a.take<uint16_t>(cnt[4]);  b.len[4] = cnt[4] * 2;
+    b.p[5] = (char*)a.take<unsigned long long>(cnt[5]);  b.len[5] = cnt[5] * 8;
+    return b;
+}
+
+static void arena_case() {
+    rr::Arena m;
+    const ArenaBlocks mb = arena_blocks(m);
+    for (char* p : mb.p) EXPECT(p == nullptr);                 // measuring hands out nothing
+    const size_t need = m.bytes();
+    EXPECT(need >= 256 + 1200 + 1 + 616 + 2000 + 40 && need % 256 == 0);
+    EXPECT(rr::Arena().bytes() == 256);                        // the base slack alone
+    std::vector<char> host(need + 512);                        // ASan guards both ends
+    char* base = host.data() + (256 - (uintptr_t)host.data() % 256) % 256 + 8;   // 8 bytes off a 256 boundary
+    rr::Arena c(base, need);
+    const ArenaBlocks cb = arena_blocks(c);
+    EXPECT(c.bytes() == need && c.fits());
+    for (int i = 0; i < 6; ++i) {
+        EXPECT(cb.p[i] != nullptr && (uintptr_t)cb.p[i] % 256 == 0);
+        EXPECT(cb.p[i] >= base && cb.p[i] + cb.len[i] <= base + need);
+        for (int j = 0; j < i; ++j) EXPECT(cb.p[j] + cb.len[j] <= cb.p[i]);   // disjoint, in order
+        std::memset(cb.p[i], 0x5a, cb.len[i]);                 // inside the host buffer, or ASan reports it
+    }
+    rr::Arena tight(base, need - 1);
+    arena_blocks(tight);
+    EXPECT(tight.bytes() == need && !tight.fits());
+    for (rr::Arena* a : {&m, &c}) {                            // count * sizeof(T) overflows: saturate, never wrap
+        EXPECT(a->take<double>(SIZE_MAX / 4) == nullptr);
+        EXPECT(a->bytes() == SIZE_MAX && !a->fits());
+        EXPECT(a->take<char>(1) == nullptr && a->bytes() == SIZE_MAX);
+    }
+    rr::Arena edge(base, SIZE_MAX);                            // the sum overflows, the product does not
+    edge.take<char>(1);
+    EXPECT(edge.take<char>(SIZE_MAX - 300) == nullptr && edge.bytes() == SIZE_MAX && !edge.fits());
+}
+
 int main() {
     EXPECT(rr_version() > 0);
+    arena_case();
     EXPECT(rr_last_error() != nullptr);
 
     // --- workspace sizing
