@@ -8,6 +8,7 @@ There is deliberately no CPU fallback: if librr.so cannot be loaded, or a
 tensor is not on the GPU, the call raises.
 """
 
+import contextlib
 import ctypes
 import os
 import threading
@@ -24,6 +25,11 @@ RR_CONV_AFFINE, RR_CONV_RESIDUAL, RR_CONV_PERM32 = 1, 2, 4
 RR_NHWC, RR_NCHW = 0, 1
 RR_MATCH_NN, RR_MATCH_MNN, RR_MATCH_SNN, RR_MATCH_SMNN = 0, 1, 2, 3
 RR_RESP_HARRIS, RR_RESP_GFTT, RR_RESP_HESSIAN, RR_RESP_DOG = 0, 1, 2, 3
+# enum rr_tune_key, in order: RR_TUNE_<name> = index
+TUNE_KEYS = ("GEMM_CONFIG", "GEMM_STAGES", "GEMM_WIDE", "GEMM_ASTAT", "GEMM_XCD_MAP", "STREAM_1X1", "CONV3X3",
+             "GRID_CUS", "GEMM8", "KNN_FUSED", "CONV3_PIPE", "STEM", "STREAM_XCD", "CONV3S", "WRES", "PAIR_MID",
+             "WRES_RING")
+globals().update(("RR_TUNE_" + name, key) for key, name in enumerate(TUNE_KEYS))
 
 _DTYPE_CODE = {torch.float32: RR_F32, torch.bfloat16: RR_BF16, torch.float16: RR_F16,
                torch.int8: RR_I8}  # RR_I8: kNN screening only
@@ -128,6 +134,7 @@ _SIGS = {
     "rr_rank_workspace_bytes":([_ll, _i], _sz),
     "rr_rank_full": ([_vp, _ll, _vp, _i, _i, _vp, _vp, _sz, _vp], _i),
     "rr_set_tuning": ([_i, _i], _i),
+    "rr_get_tuning": ([_i, ctypes.POINTER(_i)], _i),
     "rr_fill_unit_rows": ([_vp, _ll, _i, ctypes.c_ulonglong, _ll, _vp], _i),
     "rr_cast_f32_bf16": ([_vp, _vp, _ll, _vp], _i),
     "rr_cast_f32_f16": ([_vp, _vp, _ll, _vp], _i),
@@ -163,6 +170,50 @@ def check(rc, what):
     if rc != 0:
         msg = lib().rr_last_error().decode(errors="replace")
         raise RuntimeError("%s failed (rc=%d): %s" % (what, rc, msg))
+
+
+def _tune_key(name):
+    """'WRES', 'RR_TUNE_WRES', 'wres' or '14' -> 14."""
+    name = str(name).upper()
+    name = name[len("RR_TUNE_"):] if name.startswith("RR_TUNE_") else name
+    if name in TUNE_KEYS:
+        return TUNE_KEYS.index(name)
+    try:
+        return int(name)
+    except ValueError:
+        raise ValueError("unknown tuning key %r (one of %s, or a number)" % (name, ", ".join(TUNE_KEYS)))
+
+
+def get_tuning(key):
+    value = ctypes.c_int()
+    check(lib().rr_get_tuning(_tune_key(key), ctypes.byref(value)), "rr_get_tuning")
+    return value.value
+
+
+def set_tuning(key, value):
+    check(lib().rr_set_tuning(_tune_key(key), int(value)), "rr_set_tuning")
+
+
+@contextlib.contextmanager
+def tuning(**values):
+    """with tuning(WRES=0, GEMM8=1 | 8): ... -- set the named rr_tune_key knobs for the
+    body and put back the values they had, in reverse order, however the body ends."""
+    saved = []
+    try:
+        for name, value in values.items():
+            saved.append((name, get_tuning(name)))
+            set_tuning(name, value)
+        yield
+    finally:
+        for name, value in reversed(saved):
+            set_tuning(name, value)
+
+
+def apply_tuning_arg(arg):
+    """A command line's --tune "k=v,k=v" (keys by name or number), set for the process."""
+    for kv in filter(None, (arg or "").split(",")):
+        key, value = kv.split("=")
+        set_tuning(key.strip(), int(value, 0))
 
 
 def stream_ptr(device=None):

@@ -297,18 +297,8 @@ static void launch(const ConvArgs& a, bool k1, hipStream_t s) {
 }
 
 template <typename T, typename TO> void launch_gemm2(const ConvArgs& a, bool k1, hipStream_t s);
-extern int g_knn_fused;  // rr_knn.hip
 bool launch_stream1x1(const ConvArgs& a, hipStream_t s, bool f16);  // rr_stream.hip
 bool launch_conv3x3(const ConvArgs& a, hipStream_t s, bool f16);    // rr_conv3.hip
-extern int g_stream_mode;
-extern int g_conv3_mode;
-extern int g_conv3_pipe;
-extern int g_stem_mode;
-extern int g_stream_xcd;
-extern int g_conv3s;
-extern int g_wres;
-extern int g_pair_mid;
-extern int g_wres_ring;
 
 // out[R][k] = w[chan(R)][ci][kh][kw] with k = (kh*KW + kw)*cin_pad + ci, zeros elsewhere.
 template <typename T>
@@ -441,31 +431,4 @@ extern "C" int rr_pack_conv_weights(const float* w, int c_out, int c_in, int kh,
     else
         return fail(RR_EINVAL, "rr_pack_conv_weights: dtype");
     return check_launch("rr_pack_conv_weights");
-}
-
-namespace rr {
-void set_gemm_tuning(int key, int value);
-}
-extern "C" int rr_set_tuning(int key, int value) {
-    if (key < 0 || key > 16) return fail(RR_EINVAL, "rr_set_tuning: unknown key");
-    if (key == RR_TUNE_KNN_FUSED) {
-        rr::g_knn_fused = value != 0;
-        return RR_OK;
-    }
-    if (key == RR_TUNE_GRID_CUS) {
-        if (value < 0) return fail(RR_EINVAL, "rr_set_tuning: RR_TUNE_GRID_CUS must be >= 0");
-        rr::g_grid_cap = value;
-        return RR_OK;
-    }
-    if (key == RR_TUNE_STREAM_1X1) rr::g_stream_mode = value;
-    else if (key == RR_TUNE_CONV3X3) rr::g_conv3_mode = value;
-    else if (key == RR_TUNE_CONV3_PIPE) rr::g_conv3_pipe = value;
-    else if (key == RR_TUNE_STEM) rr::g_stem_mode = value;
-    else if (key == RR_TUNE_STREAM_XCD) rr::g_stream_xcd = value;
-    else if (key == RR_TUNE_CONV3S) rr::g_conv3s = value;
-    else if (key == RR_TUNE_WRES) rr::g_wres = value;
-    else if (key == RR_TUNE_PAIR_MID) rr::g_pair_mid = value;
-    else if (key == RR_TUNE_WRES_RING) rr::g_wres_ring = value;
-    else rr::set_gemm_tuning(key, value);
-    return RR_OK;
 }

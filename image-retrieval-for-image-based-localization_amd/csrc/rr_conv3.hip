@@ -618,10 +618,6 @@ __global__ void __launch_bounds__(512, 1) k_c3w64(ConvArgs a, int tiles_w, int t
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-}  // namespace
-int g_conv3_pipe = 1;  // rr_set_tuning(RR_TUNE_CONV3_PIPE): 1 software-pipelined A-stationary tiles, 0 compiler schedule
-namespace {
-
 template <int TC, int TH, int TW, int WC, int WP, bool ARES, int NSA = 2>
 void launch_c3(const ConvArgs& a, hipStream_t s, bool f16) {
     const int tiles_w = a.w_ / TW, tiles_h = a.h / TH, tiles_c = a.cout / TC;
@@ -629,7 +625,7 @@ void launch_c3(const ConvArgs& a, hipStream_t s, bool f16) {
     const int cus = grid_cus();
     const int grid = (int)(ntl < cus ? ntl : cus);
     // the overlapped epilogue's branch-free activation needs slope in [0, 1]
-    const int pipe = g_conv3_pipe && (a.act != RR_ACT_LEAKY || (a.slope >= 0.f && a.slope <= 1.f));
+    const int pipe = g_tune.conv3_pipe && (a.act != RR_ACT_LEAKY || (a.slope >= 0.f && a.slope <= 1.f));
     if (f16)
         hipLaunchKernelGGL((k_conv3x3<TC, TH, TW, WC, WP, ARES, NSA, f16_t>), dim3(grid), dim3(64 * WC * WP), 0, s, a,
                            tiles_w, tiles_w * tiles_h, tiles_c, (int)ntl, pipe);
@@ -640,11 +636,6 @@ void launch_c3(const ConvArgs& a, hipStream_t s, bool f16) {
 
 }  // namespace
 
-int g_c3w64 = 1;       // mod2 3x3 on k_c3w64 under RR_TUNE_CONV3X3 = 1 (9 forces it)
-int g_conv3_mode = 1;  // rr_set_tuning(RR_TUNE_CONV3X3): 0 off, 1 auto, 2 / 3 prefer 8x32 / 4x32 tiles,
-                       // 4 / 6 A-stationary with 1x8 / 1x4 waves (auto: 2x4), 7 3-stage weight ring,
-                       // 8 256-channel x 6x32 tiles (auto where c_out % 256 == 0 and h % 6 == 0)
-
 // bf16 3x3 / stride 1 / pad 1 with PERM32 weights, bf16 out, no residual, and
 // image sizes the tiles divide; returns false otherwise (caller falls back to
 // the implicit-GEMM engine).
@@ -652,9 +643,10 @@ bool gemm8_eligible(const ConvArgs& a, bool k1, int esz);  // rr_gemm.hip
 bool launch_conv3s(const ConvArgs& a, hipStream_t s, bool f16);  // rr_conv3s.hip
 
 bool launch_conv3x3(const ConvArgs& a, hipStream_t s, bool f16) {
-    if (g_conv3_mode == 0) return false;
+    const int mode = g_tune.conv3x3;
+    if (mode == 0) return false;
     // the staggered two-wave-group kernel (c_out = 128, or c_in = c_out = 64)
-    if (g_conv3_mode == 1 && launch_conv3s(a, s, f16)) return true;
+    if (mode == 1 && launch_conv3s(a, s, f16)) return true;
     if (a.kh != 3 || a.kw != 3 || a.stride != 1 || a.pad != 1 || a.dil != 1) return false;
     if (!(a.flags & RR_CONV_PERM32) || (a.flags & RR_CONV_RESIDUAL) || a.ldy != a.cout) return false;
     if (a.cin % 64 || a.kp != 9 * a.cin || a.w_ % 32) return false;
@@ -663,9 +655,9 @@ bool launch_conv3x3(const ConvArgs& a, hipStream_t s, bool f16) {
     // 256-multiple output channels on a chip-filling problem (mod4 / mod5 3x3 at
     // 128 images): the 8-phase GEMM on tap-uniform im2col beats the direct
     // kernel (420 vs 479, 392 vs 455 us) — the taps re-read from L2
-    if (a.cout % 256 == 0 && g_conv3_mode == 1 && gemm8_eligible(a, false, 2)) return false;
+    if (a.cout % 256 == 0 && mode == 1 && gemm8_eligible(a, false, 2)) return false;
     const int g_c3_cus = grid_cus();
-    if (a.cin == 64 && a.cout == 64 && a.h % 8 == 0 && (g_conv3_mode == 9 || (g_conv3_mode == 1 && g_c3w64))) {
+    if (a.cin == 64 && a.cout == 64 && a.h % 8 == 0 && (mode == 9 || mode == 1)) {
         const int tiles_w = a.w_ / 32, tiles_hw = tiles_w * (a.h / 8);
         const long long ntl = (long long)a.n * tiles_hw;
         int grid = (int)(ntl < g_c3_cus ? ntl : g_c3_cus) & ~7;
@@ -676,8 +668,8 @@ bool launch_conv3x3(const ConvArgs& a, hipStream_t s, bool f16) {
     }
     if (a.cin == 64 && a.cout == 64 && a.h % 8 == 0) {
         // 8 waves (2 per SIMD) measured fastest: 125 us vs 146 (4 waves) at 32 x 192x256x64
-        if (g_conv3_mode == 4) launch_c3<64, 8, 32, 1, 8, true>(a, s, f16);
-        else if (g_conv3_mode == 6) launch_c3<64, 8, 32, 1, 4, true>(a, s, f16);
+        if (mode == 4) launch_c3<64, 8, 32, 1, 8, true>(a, s, f16);
+        else if (mode == 6) launch_c3<64, 8, 32, 1, 4, true>(a, s, f16);
         else launch_c3<64, 8, 32, 2, 4, true>(a, s, f16);
         return true;
     }
@@ -685,15 +677,15 @@ bool launch_conv3x3(const ConvArgs& a, hipStream_t s, bool f16) {
         // 8 x 32 tiles when they still give every CU two or more tiles, else 4 x 32
         // (tuning modes 2 / 3 force one of them where the image height allows)
         const long long t8 = a.h % 8 == 0 ? (long long)a.n * (a.h / 8) * (a.w_ / 32) * (a.cout / 128) : 0;
-        const bool want8 = g_conv3_mode == 2 || (g_conv3_mode != 3 && t8 >= 2 * g_c3_cus);
+        const bool want8 = mode == 2 || (mode != 3 && t8 >= 2 * g_c3_cus);
         // 256-channel tiles x 6 x 32 pixels (half the patch re-reads across channel
         // tiles, 48 MFMAs per wave between barriers) for c_out % 256 == 0
         // (measured at 128 x R50: mod4 c2 505 -> 461 us, mod5 c2 472 -> 416 us; default where it applies)
-        if ((g_conv3_mode == 1 || g_conv3_mode == 8) && a.cout % 256 == 0 && a.h % 6 == 0) {
+        if ((mode == 1 || mode == 8) && a.cout % 256 == 0 && a.h % 6 == 0) {
             launch_c3<256, 6, 32, 4, 2, false>(a, s, f16);
             return true;
         }
-        const bool deep = g_conv3_mode == 7;  // 3-stage weight ring
+        const bool deep = mode == 7;  // 3-stage weight ring
         if (t8 > 0 && (want8 || a.h % 4 != 0)) {
             if (deep) launch_c3<128, 8, 32, 2, 4, false, 3>(a, s, f16);
             else launch_c3<128, 8, 32, 2, 4, false>(a, s, f16);

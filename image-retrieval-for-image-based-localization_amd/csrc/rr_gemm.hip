@@ -534,24 +534,10 @@ __global__ void __launch_bounds__(64 * WC * WP, ((NS == 2 && AK * TC <= 256) || 
     }
 }
 
-static int g_stages = 0;
-static bool g_wide = true;
-static bool g_ast = false;
-static bool g_xmap = false;
-static bool g_prio = false;
-static bool g_env_done = false;
-
-static int num_cus() {
-    if (!g_env_done) {
-        const char* e = getenv("RR_GEMM_STAGES");
-        g_stages = (e && (e[0] == '3')) ? 3 : 2;
-        const char* w = getenv("RR_GEMM_WIDE");
-        g_wide = !(w && w[0] == '0');
-        const char* pr = getenv("RR_GEMM_PRIO");
-        g_prio = pr && pr[0] == '1';
-        g_env_done = true;
-    }
-    return grid_cus();
+// k_igemm's xmap argument: bit 0 RR_TUNE_GEMM_XCD_MAP, bit 1 RR_GEMM_PRIO=1
+static int igemm_xmap() {
+    static const bool prio = getenv("RR_GEMM_PRIO") && getenv("RR_GEMM_PRIO")[0] == '1';
+    return (g_tune.gemm_xcd_map ? 1 : 0) | (prio ? 2 : 0);
 }
 
 template <typename T, typename TO, int TC, int TP, int WC, int WP, int NS, int AK = 0>
@@ -561,20 +547,20 @@ static void launch_ns(const ConvArgs& a, bool k1, bool perm, hipStream_t s) {
     const int tiles_p = (a.P + TP - 1) / TP;
     const int tiles_c = (a.cout + TC - 1) / TC;
     const int ntiles = tiles_p * tiles_c;
-    const int cap = PER_CU * num_cus();
+    const int cap = PER_CU * grid_cus();
     const int grid = ntiles < cap ? ntiles : cap;
     const int km = k1 ? 1 : ((a.cin * (int)sizeof(T)) % 128 == 0 && tapu_ok(a.kh * a.kw, (long long)a.kp * (int)sizeof(T) / 128)) ? 2 : 0;
 #define RR_L3(PV)                                                                                                    \
     do {                                                                                                             \
         if (km == 1)                                                                                                 \
             hipLaunchKernelGGL((k_igemm<T, TO, TC, TP, WC, WP, 1, PV, NS, AK>), dim3(grid), dim3(64 * WC * WP), 0, s, \
-                               a, tiles_p, ntiles, (g_xmap ? 1 : 0) | (g_prio ? 2 : 0));                                                  \
+                               a, tiles_p, ntiles, igemm_xmap());                                                    \
         else if (km == 2)                                                                                            \
             hipLaunchKernelGGL((k_igemm<T, TO, TC, TP, WC, WP, 2, PV, NS, AK>), dim3(grid), dim3(64 * WC * WP), 0, s, \
-                               a, tiles_p, ntiles, (g_xmap ? 1 : 0) | (g_prio ? 2 : 0));                                                  \
+                               a, tiles_p, ntiles, igemm_xmap());                                                    \
         else                                                                                                         \
             hipLaunchKernelGGL((k_igemm<T, TO, TC, TP, WC, WP, 0, PV, NS, AK>), dim3(grid), dim3(64 * WC * WP), 0, s, \
-                               a, tiles_p, ntiles, (g_xmap ? 1 : 0) | (g_prio ? 2 : 0));                                                  \
+                               a, tiles_p, ntiles, igemm_xmap());                                                    \
     } while (0)
     if constexpr (std::is_same<T, TO>::value && (TC / WC / 16) % 2 == 0) {
         if (perm) {
@@ -588,9 +574,8 @@ static void launch_ns(const ConvArgs& a, bool k1, bool perm, hipStream_t s) {
 
 template <typename T, typename TO, int TC, int TP, int WC, int WP>
 static void launch_cfg3(const ConvArgs& a, bool k1, bool perm, hipStream_t s) {
-    num_cus();
     if constexpr (3 * (TC + TP) * 128 <= 160 * 1024 && WC * WP == 4) {
-        if (g_stages == 3) {
+        if (g_tune.gemm_stages == 3) {
             launch_ns<T, TO, TC, TP, WC, WP, 3>(a, k1, perm, s);
             return;
         }
@@ -1676,21 +1661,12 @@ __global__ void __launch_bounds__(512, 1) k_gemm8a(ConvArgs a, int tiles_p, int 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-static int g_gemm8 = -1;  // rr_set_tuning(RR_TUNE_GEMM8) / RR_GEMM8: 0 off, 1 auto (default), 2 force where legal
-static bool g_gemm8_tile = false;  // RR_TUNE_GEMM8 value | 4: one block per tile instead of persistent blocks
-static bool g_gemm8_pmajor = true;  // RR_TUNE_GEMM8 value | 64: conv tiles channel-major
-static bool g_gemm8_short_persist = true;  // RR_TUNE_GEMM8 value | 512: short-K 1x1 convs one block per tile
-
 // 16-bit operands, 1x1 or tap-uniform im2col, an even number of 64-deep
 // K-steps, 31-bit operand offsets, and (auto) enough 256 x 256 tiles to fill
 // the chip twice with no half-empty channel tile (c_out = 128 would waste
 // half the MFMAs).
 bool gemm8_eligible(const ConvArgs& a, bool k1, int esz) {
-    if (g_gemm8 < 0) {
-        const char* e = getenv("RR_GEMM8");
-        g_gemm8 = (e && e[0] == '0') ? 0 : 1;
-    }
-    if (!g_gemm8 || esz != 2) return false;
+    if (!g_tune.gemm8_mode() || esz != 2) return false;
     const int km = k1 ? 1 : ((a.cin * 2) % 128 == 0 && tapu_ok(a.kh * a.kw, a.kp / 64)) ? 2 : 0;
     const int nk = a.kp / 64;
     if (km == 0 || nk < 2 || (nk & 1) || a.kp % 64) return false;
@@ -1699,7 +1675,7 @@ bool gemm8_eligible(const ConvArgs& a, bool k1, int esz) {
     const long long ntiles = (long long)((a.P + 255) / 256) * ((a.cout + 255) / 256);
     // (a partial last channel tile is negligible for long channel dims, e.g. the
     // database rows of the kNN score GEMM)
-    if (g_gemm8 == 1 && (a.P < 256 || ntiles < 2 * grid_cus() || (a.cout % 256 && a.cout < 4096))) return false;
+    if (g_tune.gemm8_mode() == 1 && (a.P < 256 || ntiles < 2 * grid_cus() || (a.cout % 256 && a.cout < 4096))) return false;
     return true;
 }
 
@@ -1725,13 +1701,13 @@ static bool try_gemm8(const ConvArgs& a, bool k1, bool perm, hipStream_t s) {
         // (128 x R50 layers, same box: K = 512 540 -> 521 / 579 -> 552 us, K = 1024
         // neutral to -8 us; K = 2048 and the 3x3s measured slower, so they stay one block
         // per tile).
-        const bool short_k1 = g_gemm8_short_persist && k1 && a.kp / 64 <= 16 && !(a.flags & RR_CONV_RESIDUAL);
-        const bool persist = !g_gemm8_tile && (g_gemm8 == 2 || !std::is_same<T, TO>::value ||
-                                               (std::is_same<T, TO>::value && short_k1));
+        const bool short_k1 = g_tune.gemm8_short_persist() && k1 && a.kp / 64 <= 16 && !(a.flags & RR_CONV_RESIDUAL);
+        const bool persist = !g_tune.gemm8_tile() && (g_tune.gemm8_mode() == 2 || !std::is_same<T, TO>::value ||
+                                                      (std::is_same<T, TO>::value && short_k1));
         // (a grid below 8 blocks would leave some XCD's tile range without a block)
         const dim3 g((unsigned)(!persist || cus < 8 || ntiles < cus ? ntiles : cus)), b(512);
         // conv GEMMs (16-bit out) walk their tiles pixel-major (RR_TUNE_GEMM8 | 64: channel-major)
-        const int pmajor = std::is_same<T, TO>::value && g_gemm8_pmajor && tiles_c > 1;
+        const int pmajor = std::is_same<T, TO>::value && g_tune.gemm8_pmajor() && tiles_c > 1;
 #define RR_G8(KMV, PV) hipLaunchKernelGGL((k_gemm8<T, TO, KMV, PV>), g, b, 0, s, a, tiles_p, (int)ntiles, pmajor)
         if constexpr (std::is_same<T, TO>::value) {
             if (perm) {
@@ -1747,9 +1723,6 @@ static bool try_gemm8(const ConvArgs& a, bool k1, bool perm, hipStream_t s) {
     }
 }
 
-static int g_gemm8h = 1;  // rr_set_tuning(RR_TUNE_GEMM8, value | 8): k_gemm8h off
-static int g_gemm8s = 1;  // rr_set_tuning(RR_TUNE_GEMM8, value | 32): k_gemm8h instead of k_gemm8s
-
 // k_gemm8h: 16-bit 1x1 score GEMM (float out, natural row order, no affine /
 // residual / activation) with <= 128 "pixels" (queries), long channel dim.
 template <typename T, typename TO>
@@ -1757,13 +1730,13 @@ static bool try_gemm8h(const ConvArgs& a, bool k1, bool perm, hipStream_t s) {
     if constexpr (sizeof(T) != 2 || !std::is_same<TO, float>::value) {
         return false;
     } else {
-        if (!g_gemm8h || !k1 || perm || a.kp % 64 || a.kp != a.cin || a.kp / 64 < 2) return false;
+        if (!g_tune.gemm8h() || !k1 || perm || a.kp % 64 || a.kp != a.cin || a.kp / 64 < 2) return false;
         if (a.flags & (RR_CONV_AFFINE | RR_CONV_RESIDUAL) || a.act != RR_ACT_IDENTITY) return false;
         if (a.P < 1 || a.P > 128 || (long long)a.P * a.cin * 2 >= (1ll << 31) || 256ll * a.kp * 2 >= (1ll << 31))
             return false;
         const long long ntiles = ((long long)a.cout + 255) / 256;
         if (ntiles >= (1ll << 31)) return false;
-        if (g_gemm8s) {
+        if (g_tune.gemm8s()) {
             // persistent streaming form: one block per CU (a grid below 8 blocks
             // would leave some XCD's tile range without a block)
             const long long cus = grid_cus();
@@ -1784,13 +1757,10 @@ static bool try_gemm8h(const ConvArgs& a, bool k1, bool perm, hipStream_t s) {
     }
 }
 
-static int g_gemm8a = 1;  // rr_set_tuning(RR_TUNE_GEMM8, value | 16): k_gemm8a off
-static bool g_gemm8a_tile = false;  // RR_TUNE_GEMM8 value | 128: k_gemm8a one block per tile
-
 // k_gemm8a: 16-bit PERM32 convs with 128-multiple c_out below 256 (1x1 or
 // tap-uniform im2col), enough 128 x 256 tiles to fill the chip twice.
 bool gemm8a_eligible(const ConvArgs& a, bool k1) {
-    if (!g_gemm8a || !(a.flags & RR_CONV_PERM32) || a.cout % 128 || a.cout >= 256) return false;
+    if (!g_tune.gemm8a() || !(a.flags & RR_CONV_PERM32) || a.cout % 128 || a.cout >= 256) return false;
     const int km = k1 ? 1 : ((a.cin * 2) % 128 == 0 && tapu_ok(a.kh * a.kw, a.kp / 64)) ? 2 : 0;
     if (km == 0 || a.kp % 64 || a.kp / 64 < 2) return false;
     if ((long long)a.n * a.h * a.w_ * a.cin * 2 >= (1ll << 31) || 128ll * a.kp * 2 >= (1ll << 31)) return false;
@@ -1809,7 +1779,7 @@ static bool try_gemm8a(const ConvArgs& a, bool k1, bool perm, hipStream_t s) {
         // persistent (RR_TUNE_GEMM8 value | 128: one block per tile)
         // (a grid below 8 blocks would leave some XCD's tile range without a block)
         const int cus = grid_cus();
-        const int grid = g_gemm8a_tile || cus < 8 || ntiles < cus ? ntiles : cus;
+        const int grid = g_tune.gemm8a_tile() || cus < 8 || ntiles < cus ? ntiles : cus;
         if (k1) hipLaunchKernelGGL((k_gemm8a<T, 1>), dim3(grid), dim3(512), 0, s, a, tiles_p, ntiles);
         else hipLaunchKernelGGL((k_gemm8a<T, 2>), dim3(grid), dim3(512), 0, s, a, tiles_p, ntiles);
         return true;
@@ -1839,14 +1809,12 @@ int gemm_scores_i8(const ConvArgs& a, hipStream_t s) {
     return RR_OK;
 }
 
-int g_force_cfg = 0;  // rr_set_tuning(RR_TUNE_GEMM_CONFIG, ...)
-
 template <typename T, typename TO>
 void launch_gemm2(const ConvArgs& a, bool k1, hipStream_t s) {
     const bool perm = (a.flags & RR_CONV_PERM32) != 0;
     const bool resid = (a.flags & RR_CONV_RESIDUAL) != 0;
-    num_cus();
-    switch (g_force_cfg) {
+    const int force_cfg = g_tune.gemm_config;
+    switch (force_cfg) {
         case 1: launch_cfg3<T, TO, 128, 128, 2, 2>(a, k1, perm, s); return;
         case 2: launch_cfg3<T, TO, 64, 256, 1, 4>(a, k1, perm, s); return;
         case 3: launch_cfg3<T, TO, 256, 128, 4, 2>(a, k1, perm, s); return;
@@ -1856,11 +1824,11 @@ void launch_gemm2(const ConvArgs& a, bool k1, hipStream_t s) {
         case 8: launch_ns<T, TO, 128, 256, 2, 4, 3>(a, k1, perm, s); return;  // 8 waves, 3-stage ring (144 KiB)
         default: break;
     }
-    if (g_force_cfg == 0 && try_gemm8<T, TO>(a, k1, perm, s)) return;
-    if (g_force_cfg == 0 && try_gemm8a<T, TO>(a, k1, perm, s)) return;
+    if (force_cfg == 0 && try_gemm8<T, TO>(a, k1, perm, s)) return;
+    if (force_cfg == 0 && try_gemm8a<T, TO>(a, k1, perm, s)) return;
     // A-stationary variants (single output-channel tile, short K)
     const int nk = a.kp / (sizeof(T) == 2 ? 64 : 32);
-    if (g_force_cfg == 6 || (g_force_cfg == 0 && g_ast)) {
+    if (force_cfg == 6 || (force_cfg == 0 && g_tune.gemm_astat)) {
         if (a.cout > 128 && a.cout <= 256 && nk <= 1 && a.P > 64) {
             launch_ns<T, TO, 256, 64, 4, 1, 2, 1>(a, k1, perm, s);
             return;
@@ -1883,7 +1851,7 @@ void launch_gemm2(const ConvArgs& a, bool k1, hipStream_t s) {
         launch_cfg3<T, TO, 128, 128, 2, 2>(a, k1, perm, s);
     else if (a.cout <= 64)
         launch_cfg3<T, TO, 64, 256, 1, 4>(a, k1, perm, s);
-    else if (a.cout <= 128 || !g_wide)
+    else if (a.cout <= 128 || !g_tune.gemm_wide)
         launch_cfg3<T, TO, 128, 128, 2, 2>(a, k1, perm, s);
     else if (resid && a.cout <= 256 && nk <= 1)
         launch_ns<T, TO, 256, 64, 4, 1, 2, 1>(a, k1, perm, s);
@@ -1893,26 +1861,6 @@ void launch_gemm2(const ConvArgs& a, bool k1, hipStream_t s) {
         launch_cfg3<T, TO, 256, 64, 4, 1>(a, k1, perm, s);
     else
         launch_cfg3<T, TO, 256, 256, 4, 2>(a, k1, perm, s);
-}
-
-void set_gemm_tuning(int key, int value) {
-    num_cus();
-    if (key == RR_TUNE_GEMM_CONFIG) g_force_cfg = value;
-    else if (key == RR_TUNE_GEMM_STAGES) g_stages = value == 3 ? 3 : 2;
-    else if (key == RR_TUNE_GEMM_WIDE) g_wide = value != 0;
-    else if (key == RR_TUNE_GEMM_ASTAT) g_ast = value != 0;
-    else if (key == RR_TUNE_GEMM_XCD_MAP) g_xmap = value != 0;
-    else if (key == RR_TUNE_GEMM8) {
-        g_gemm8h = !(value >= 0 && (value & 8));
-        g_gemm8a = !(value >= 0 && (value & 16));
-        g_gemm8s = !(value >= 0 && (value & 32));
-        g_gemm8_tile = value >= 0 && (value & 4);
-        g_gemm8_pmajor = !(value >= 0 && (value & 64));
-        g_gemm8_short_persist = !(value >= 0 && (value & 512));
-        g_gemm8a_tile = value >= 0 && (value & 128);
-        value = value < 0 ? 0 : value & 3;
-        g_gemm8 = value > 2 ? 2 : value;
-    }
 }
 
 template void launch_gemm2<bf16_t, bf16_t>(const ConvArgs&, bool, hipStream_t);

@@ -7,6 +7,7 @@
 #include <string>
 
 #include "../../include/rr.h"
+#include "rr_tuning.h"
 
 namespace rr {
 
@@ -19,7 +20,6 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 // rr_set_tuning(RR_TUNE_GRID_CUS, n) (0 = no cap) so that launches on two
 // streams can share the chip (rr_runtime.hip).
 int grid_cus();
-extern int g_grid_cap;
 
 // A ragged image batch (a cirtorch PackedSequence at the model boundary,
 // utils/parallel/packed_sequence.py:8-96): image i of a launch is [c][h_i][w_i]

@@ -44,7 +44,6 @@ static size_t slab_budget() {
 typedef __attribute__((ext_vector_type(4))) float f32x4_knn_t;
 constexpr int MAX_SORT = 8192;
 constexpr int PREFIX_CHUNKS = 4;         // chunks through the slab path before the screening GEMM
-int g_knn_fused = 1;                     // rr_set_tuning(RR_TUNE_KNN_FUSED)
 constexpr int TOPK_BINS = 2048;          // radix-select histogram (11-bit digits)
 
 __device__ __forceinline__ uint32_t fkey(float f) {
@@ -964,12 +963,11 @@ static int knn_topk_impl(const void* db, const float* db_f32, long long n_db, co
     // scores >= tau to per-(query, chunk) slots (no slab write / read, no
     // select launch); overflowing slots are rebuilt by k_slot_fixup.
     // RR_KNN_FUSED=0: every chunk through the slab (the round-1 pipeline).
-    static const int fused_env = getenv("RR_KNN_FUSED") && getenv("RR_KNN_FUSED")[0] == '0' ? 0 : 1;
     // RR_KNN_PREFIX: prefix chunks (A/B knob; any count gives the same results -- tau is
     // a valid bound whatever the prefix, and overflowing slots are rebuilt)
     static const int prefix = getenv("RR_KNN_PREFIX") ? atoi(getenv("RR_KNN_PREFIX")) : PREFIX_CHUNKS;
     const int pre = prefix >= 1 ? prefix : PREFIX_CHUNKS;
-    const bool fused = fused_env && g_knn_fused && p.nchunks > pre && (d * esz) % 128 == 0;
+    const bool fused = g_tune.knn_fused && p.nchunks > pre && (d * esz) % 128 == 0;
     const int g0 = fused ? pre : p.nchunks;
     const long long slab_rows = (long long)g0 * p.L < n_db ? (long long)g0 * p.L : n_db;
     // the running threshold is reset by a kernel (RR_KNN_TAU_MEMSET=1: by

@@ -9,7 +9,38 @@ namespace rr {
 
 static thread_local std::string g_err;
 
-int g_grid_cap = 0;
+// Store a key's value in the rr_set_tuning encoding, normalised as documented
+// in rr.h; returns an error message or nullptr.
+static const char* tune_store(Tuning& t, int key, int v) {
+    switch (key) {
+        case RR_TUNE_GEMM_STAGES: v = v == 3 ? 3 : 2; break;
+        case RR_TUNE_GEMM_WIDE:
+        case RR_TUNE_GEMM_ASTAT:
+        case RR_TUNE_GEMM_XCD_MAP: v = v != 0; break;
+        case RR_TUNE_KNN_FUSED: v = v != 0 && !t.knn_fused_env_off; break;
+        case RR_TUNE_GRID_CUS:
+            if (v < 0) return "rr_set_tuning: RR_TUNE_GRID_CUS must be >= 0";
+            break;
+        case RR_TUNE_GEMM8: v = v < 0 ? 0 : ((v & 3) > 2 ? 2 : (v & 3)) | (v & Tuning::GEMM8_FLAGS); break;
+        default: break;
+    }
+    t.*TUNE_KEYS[key].member = v;
+    return nullptr;
+}
+
+// The defaults, then the keyed environment variables by their first character:
+// RR_GEMM_STAGES "3" -> 3, anything else 2; the others "0" -> 0, anything else 1.
+static Tuning tuning_from_env() {
+    Tuning t;
+    for (int key = 0; key < TUNE_NKEYS; ++key) {
+        const char* e = TUNE_KEYS[key].env ? getenv(TUNE_KEYS[key].env) : nullptr;
+        if (e) tune_store(t, key, key == RR_TUNE_GEMM_STAGES ? (e[0] == '3' ? 3 : 2) : e[0] != '0');
+    }
+    t.knn_fused_env_off = !t.knn_fused;
+    return t;
+}
+
+Tuning g_tune = tuning_from_env();
 static int g_dev_cus = 0;
 
 int grid_cus() {
@@ -20,7 +51,7 @@ int grid_cus() {
             cus = 256;
         g_dev_cus = cus;
     }
-    return (g_grid_cap > 0 && g_grid_cap < g_dev_cus) ? g_grid_cap : g_dev_cus;
+    return (g_tune.grid_cus > 0 && g_tune.grid_cus < g_dev_cus) ? g_tune.grid_cus : g_dev_cus;
 }
 
 void set_error(const std::string& msg) { g_err = msg; }
@@ -398,6 +429,19 @@ int rr_device_arch(char* buf, int buflen) {
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return fail(RR_EHIP, "hipGetDeviceProperties failed");
     std::strncpy(buf, prop.gcnArchName, buflen - 1);
     buf[buflen - 1] = 0;
+    return RR_OK;
+}
+
+int rr_set_tuning(int key, int value) {
+    if (key < 0 || key >= TUNE_NKEYS) return fail(RR_EINVAL, "rr_set_tuning: unknown key");
+    const char* err = tune_store(g_tune, key, value);
+    return err ? fail(RR_EINVAL, err) : RR_OK;
+}
+
+int rr_get_tuning(int key, int* value) {
+    if (key < 0 || key >= TUNE_NKEYS) return fail(RR_EINVAL, "rr_get_tuning: unknown key");
+    if (!value) return fail(RR_EINVAL, "rr_get_tuning: null value");
+    *value = g_tune.*TUNE_KEYS[key].member;
     return RR_OK;
 }
 

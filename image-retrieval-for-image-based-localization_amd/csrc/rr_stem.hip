@@ -1105,38 +1105,36 @@ extern "C" int rr_stem_pack_weights(const float* w, int c_out, int c_in, int kh,
     return check_launch("rr_stem_pack_weights");
 }
 
-namespace rr {
-int g_stem_mode = 2;  // rr_set_tuning(RR_TUNE_STEM): 5 space-to-depth K (v4), 2 swapped-operand lane-local
-                      // pooling (v3; 3 / 4: 2 / 5 fill parts), 1 pool-before-epilogue kernel (v2), 0 k_stem_pool
-}
-
 // One launch over a same-size batch (TAB = NoTab, a.x = the [n][3][h][w] buffer)
 // or over <= RAGGED_MAX images of a ragged batch (TAB = RaggedTab).
 template <bool U8, typename TAB>
 static void stem_launch(const StemArgs& a, const TAB& rt, int dtype, hipStream_t st) {
     constexpr bool RG = std::is_same<TAB, RaggedTab>::value;
     const int g_stem_cus = grid_cus();
-    if (g_stem_mode >= 1 && a.ho % 2 == 0 && a.wo % 2 == 0) {  // v2/v3 handle the even stem maps (borders top / left)
+    // RR_TUNE_STEM: 5 space-to-depth K (v4), 2 swapped-operand lane-local pooling (v3; 3 / 4: 2 / 5 fill
+    // parts), 1 pool-before-epilogue kernel (v2), 0 k_stem_pool
+    const int mode = g_tune.stem;
+    if (mode >= 1 && a.ho % 2 == 0 && a.wo % 2 == 0) {  // v2/v3 handle the even stem maps (borders top / left)
         constexpr int PH = 8, PW = 56;
         const int tiles_w = (a.wp + PW - 1) / PW, tiles_h = (a.hp + PH - 1) / PH;
         const int ntiles = a.n * tiles_h * tiles_w;
         const int grid = ntiles < g_stem_cus ? ntiles : g_stem_cus;
-        if (g_stem_mode >= 2 || RG) {  // 2: patch fill in 3 parts (default), 3: 2 parts, 4: 5 parts
+        if (mode >= 2 || RG) {  // 2: patch fill in 3 parts (default), 3: 2 parts, 4: 5 parts
             auto launch = [&](auto kern) {
                 hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), 0, st, a, rt, tiles_w, tiles_w * tiles_h, ntiles);
             };
-            if (g_stem_mode == 5) {
+            if (mode == 5) {
                 if (dtype == RR_F16) launch(k_stem_pool4<f16_t, U8, 3, TAB>);
                 else launch(k_stem_pool4<bf16_t, U8, 3, TAB>);
             } else if (dtype == RR_F16) {
-                if (g_stem_mode == 3) launch(k_stem_pool3<f16_t, U8, 2, TAB>);
-                else if (g_stem_mode == 4) launch(k_stem_pool3<f16_t, U8, 5, TAB>);
-                else if (g_stem_mode == 6) launch(k_stem_pool3<f16_t, U8, 3, TAB, true>);
+                if (mode == 3) launch(k_stem_pool3<f16_t, U8, 2, TAB>);
+                else if (mode == 4) launch(k_stem_pool3<f16_t, U8, 5, TAB>);
+                else if (mode == 6) launch(k_stem_pool3<f16_t, U8, 3, TAB, true>);
                 else launch(k_stem_pool3<f16_t, U8, 3, TAB>);
             } else {
-                if (g_stem_mode == 3) launch(k_stem_pool3<bf16_t, U8, 2, TAB>);
-                else if (g_stem_mode == 4) launch(k_stem_pool3<bf16_t, U8, 5, TAB>);
-                else if (g_stem_mode == 6) launch(k_stem_pool3<bf16_t, U8, 3, TAB, true>);
+                if (mode == 3) launch(k_stem_pool3<bf16_t, U8, 2, TAB>);
+                else if (mode == 4) launch(k_stem_pool3<bf16_t, U8, 5, TAB>);
+                else if (mode == 6) launch(k_stem_pool3<bf16_t, U8, 3, TAB, true>);
                 else launch(k_stem_pool3<bf16_t, U8, 3, TAB>);
             }
             return;

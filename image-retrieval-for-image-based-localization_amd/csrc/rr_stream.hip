@@ -1069,10 +1069,6 @@ __global__ void __launch_bounds__(512, 1) k_wres1x1(WresArgs a) {
 }
 
 
-}  // namespace
-int g_stream_xcd = 1;  // rr_set_tuning(RR_TUNE_STREAM_XCD): channel slices of one strip on one XCD
-namespace {
-
 template <int TC, int K, int FN, int D, int NW, typename H>
 void launch_s_t(const ConvArgs& a, hipStream_t s) {
     const int g_stream_cus = grid_cus();
@@ -1085,21 +1081,13 @@ void launch_s_t(const ConvArgs& a, hipStream_t s) {
     const long long need = (nstrips + NW - 1) / NW;
     if (per_slice > need) per_slice = need;
     const int grid = (int)(per_slice * nslices);
-    const int xmap = g_stream_xcd && nslices > 1 && grid % (8 * nslices) == 0;
+    const int xmap = g_tune.stream_xcd && nslices > 1 && grid % (8 * nslices) == 0;
     if (a.flags & RR_CONV_RESIDUAL)
         hipLaunchKernelGGL((k_stream1x1<TC, K, FN, D, NW, true, H>), dim3(grid), dim3(64 * NW), 0, s, a, nslices, xmap);
     else
         hipLaunchKernelGGL((k_stream1x1<TC, K, FN, D, NW, false, H>), dim3(grid), dim3(64 * NW), 0, s, a, nslices, xmap);
 }
 
-}  // namespace
-
-int g_stream_mode = 1;  // rr_set_tuning(RR_TUNE_STREAM_1X1): 0 off, 1 auto, 2 / 3 see launch_stream1x1
-int g_wres = 2;         // rr_set_tuning(RR_TUNE_WRES)
-int g_pair_mid = 1;     // rr_set_tuning(RR_TUNE_PAIR_MID): 1 k_pair_mid_ring (default), 0 k_pair_mid
-int g_wres_ring = 1;    // rr_set_tuning(RR_TUNE_WRES_RING): 1 deep rings for the non-residual k_wres1x1, 0 two ahead
-
-namespace {
 template <int K, int CW>
 void launch_wres(const ConvArgs& a, hipStream_t s, bool f16) {
     constexpr int BC = 8 * CW;
@@ -1134,7 +1122,7 @@ void launch_wres(const ConvArgs& a, hipStream_t s, bool f16) {
         auto go = [&](auto h) {
             using H = decltype(h);
             if (res) hipLaunchKernelGGL((k_wres1x1<K, CW, true, H>), dim3(grid), dim3(512), 0, s, w);
-            else if (g_wres_ring) hipLaunchKernelGGL((k_wres1x1<K, CW, false, H>), dim3(grid), dim3(512), 0, s, w);
+            else if (g_tune.wres_ring) hipLaunchKernelGGL((k_wres1x1<K, CW, false, H>), dim3(grid), dim3(512), 0, s, w);
             else hipLaunchKernelGGL((k_wres1x1<K, CW, false, H, false>), dim3(grid), dim3(512), 0, s, w);
         };
         if (f16) go(f16_t{});
@@ -1154,26 +1142,26 @@ void launch_s(const ConvArgs& a, hipStream_t s, bool f16) {
 bool gemm8_eligible(const ConvArgs& a, bool k1, int esz);  // rr_gemm.hip
 
 bool launch_stream1x1(const ConvArgs& a, hipStream_t s, bool f16) {
-    if (g_stream_mode == 0) return false;
+    if (g_tune.stream_1x1 == 0) return false;
     if (!(a.flags & RR_CONV_PERM32) || a.kh != 1 || a.kw != 1 || a.pad != 0 || a.kp != a.cin) return false;
     if (a.P < 4096 || (long long)a.n * a.h * a.w_ * a.cin >= (1ll << 31)) return false;
     const bool res = a.flags & RR_CONV_RESIDUAL;
     const int K = a.cin, C = a.cout;
-    if (g_wres && (a.ldy & 7) == 0 && (a.stride == 1 ? a.h == a.ho && a.w_ == a.wo : !res)) {
+    if (g_tune.wres && (a.ldy & 7) == 0 && (a.stride == 1 ? a.h == a.ho && a.w_ == a.wo : !res)) {
         if (K == 512 && C == 2048 && res) { launch_wres<512, 32>(a, s, f16); return true; }
         if (K == 256 && C == 1024 && res) { launch_wres<256, 64>(a, s, f16); return true; }
         // the mod3 block-1 conv3 (128 -> 512 + the projection shortcut): one 512-channel slice,
         // so its input is read once (the streaming kernel's two slices re-read it)
         if (K == 128 && C == 512 && res) { launch_wres<128, 64>(a, s, f16); return true; }
-        if (g_wres >= 2) {  // the non-residual K = 256 / 512 1x1s (projections, mod4 block-1 conv1)
+        if (g_tune.wres >= 2) {  // the non-residual K = 256 / 512 1x1s (projections, mod4 block-1 conv1)
             if (K == 512 && (C == 256 || C == 1024 || C == 2048) && !res) { launch_wres<512, 32>(a, s, f16); return true; }
             if (K == 256 && (C == 512 || C == 1024) && !res) { launch_wres<256, 64>(a, s, f16); return true; }
         }
     }
     // mode 2: the residual 512 -> 2048 1x1 (mod5 conv3) on the 8-phase GEMM;
     // mode 3: also the residual 256 -> 1024 1x1 (mod4 conv3)
-    if (g_stream_mode >= 2 && K == 512 && C == 2048 && res && gemm8_eligible(a, true, 2)) return false;
-    if (g_stream_mode >= 3 && K == 256 && C == 1024 && res && gemm8_eligible(a, true, 2)) return false;
+    if (g_tune.stream_1x1 >= 2 && K == 512 && C == 2048 && res && gemm8_eligible(a, true, 2)) return false;
+    if (g_tune.stream_1x1 >= 3 && K == 256 && C == 1024 && res && gemm8_eligible(a, true, 2)) return false;
     if (K == 64 && C == 64) { launch_s<64, 64, 2, 4, 8>(a, s, f16); return true; }
     if (K == 64 && C == 256) { launch_s<256, 64, 1, 2, 8>(a, s, f16); return true; }
     if (K == 256 && C == 64) { launch_s<64, 256, 1, 4, 8>(a, s, f16); return true; }
@@ -1239,9 +1227,9 @@ extern "C" int rr_conv1x1_pair(const void* x, long long p, int c_in, const void*
             m.res = (const bf16_t*)residual + p0 * 512; m.w1 = (const bf16_t*)w1; m.s1 = scale1; m.h1 = shift1;
             m.y = (bf16_t*)y + p0 * 512; m.z = (bf16_t*)z + p0 * 128; m.P = pn;
             m.act3 = act3; m.act1 = act1; m.slope3 = slope3; m.slope1 = slope1;
-            const long long ntiles = (pn + (g_pair_mid ? 31 : 63)) / (g_pair_mid ? 32 : 64);
+            const long long ntiles = (pn + (g_tune.pair_mid ? 31 : 63)) / (g_tune.pair_mid ? 32 : 64);
             const int grid = (int)(ntiles < g_pair_cus ? ntiles : g_pair_cus);
-            if (g_pair_mid) {
+            if (g_tune.pair_mid) {
                 if (dtype == RR_F16) hipLaunchKernelGGL(k_pair_mid_ring<f16_t>, dim3(grid), dim3(512), 0, s, m);
                 else hipLaunchKernelGGL(k_pair_mid_ring<bf16_t>, dim3(grid), dim3(512), 0, s, m);
             } else {

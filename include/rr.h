@@ -855,15 +855,24 @@ int rr_rank_full(const float* db_f32, long long n, const float* q_f32, int nq, i
                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------ tuning */
-/* Engine tuning knobs (process-wide; for benchmarking / autotuning tools):
- *   RR_TUNE_GEMM_CONFIG  0 = automatic tile choice, 1 = 128x128, 2 = 64x256,
+/* Engine tuning knobs (process-wide; for benchmarking / autotuning tools).  One table
+ * (csrc/rr_tuning.h) holds every key's state and default.  rr_set_tuning stores a value
+ * after the key's normalisation (noted below; values are not range-checked otherwise) and
+ * rr_get_tuning reads it back in the same encoding, so set(key, get(key)) changes nothing.
+ * Neither makes a HIP call.  Four keys are seeded from the environment when the library
+ * loads (first character of the variable); rr_set_tuning then overrides the seed, except
+ * that RR_KNN_FUSED=0 pins RR_TUNE_KNN_FUSED to 0 for the process.
+ *   RR_TUNE_GEMM_CONFIG  0 = automatic tile choice (default), 1 = 128x128, 2 = 64x256,
  *                        3 = 256x128 (8 waves), 4 = 256x256 (8 waves), 5 = 256x64,
  *                        7 / 8 = 256x128 / 128x256 (8 waves, 3-stage ring)
  *                        6 = A-stationary (weights resident in LDS) where eligible
- *   RR_TUNE_GEMM_STAGES  2 or 3 LDS stages (3: one resident block per CU)
- *   RR_TUNE_GEMM_WIDE    0/1 allow the 8-wave tiles in the automatic choice
- *   RR_TUNE_GEMM_ASTAT   0/1 allow the A-stationary tiles in the automatic choice
- *   RR_TUNE_GEMM_XCD_MAP 0/1 XCD-contiguous tile order (default 0)
+ *   RR_TUNE_GEMM_STAGES  2 (default) or 3 LDS stages (3: one resident block per CU); any other
+ *                        value is stored as 2.  Seed: RR_GEMM_STAGES ("3": 3, else 2)
+ *   RR_TUNE_GEMM_WIDE    0/1 allow the 8-wave tiles in the automatic choice (default 1; stored
+ *                        as value != 0).  Seed: RR_GEMM_WIDE ("0": 0, else 1)
+ *   RR_TUNE_GEMM_ASTAT   0/1 allow the A-stationary tiles in the automatic choice (default 0;
+ *                        stored as value != 0)
+ *   RR_TUNE_GEMM_XCD_MAP 0/1 XCD-contiguous tile order (default 0; stored as value != 0)
  *   RR_TUNE_STREAM_1X1   0/1 weight-stationary streaming kernel for the
  *                        HBM-bound bf16 1x1 convs (default 1); 2 / 3 also route the
  *                        residual 512->2048 / 256->1024 1x1s to the 8-phase GEMM (A/B only)
@@ -875,7 +884,8 @@ int rr_rank_full(const float* db_f32, long long n, const float* q_f32, int nq, i
  *                        9 the c_in = c_out = 64 form with the weights in VGPRs
  *                        (k_c3w64; also what 1 picks for that shape)
  *   RR_TUNE_GRID_CUS     cap on the CUs one persistent launch spreads over
- *                        (0 = all; e.g. half the chip for two concurrent streams)
+ *                        (0 = all, the default; e.g. half the chip for two concurrent
+ *                        streams); a negative value is an error
  *   RR_TUNE_GEMM8        0 off, 1 auto, 2 forced: the 8-phase staggered 256x256 GEMM for eligible
  *                        16-bit 1x1 / tap-uniform convs and score GEMMs (default 1: persistent
  *                        blocks for the kNN score GEMM, one block per tile for convs; 2: also
@@ -883,15 +893,22 @@ int rr_rank_full(const float* db_f32, long long n, const float* q_f32, int nq, i
  *                        k_gemm8h / k_gemm8s; | 16: no k_gemm8a; | 32: k_gemm8h instead of the streaming
  *                        k_gemm8s for the <= 128-query score GEMM; | 64: conv tiles walked
  *                        channel-major instead of pixel-major; | 128: k_gemm8a one block per
- *                        tile instead of persistent blocks)
+ *                        tile instead of persistent blocks; | 512: the short-K non-residual
+ *                        1x1 convs one block per tile instead of persistent blocks).  Stored as
+ *                        mode | switches: a negative value as 0, mode 3 as 2, other bits
+ *                        dropped.  Seed: RR_GEMM8 ("0": 0, else 1)
  *   RR_TUNE_KNN_FUSED    0/1 kNN screening in the score-GEMM epilogue after a 4-chunk
- *                        prefix (default 1); 0 = every chunk through the score slab
+ *                        prefix (default 1; stored as value != 0); 0 = every chunk through the
+ *                        score slab.  Seed: RR_KNN_FUSED ("0": 0 for the whole process, else 1)
  *   RR_TUNE_CONV3_PIPE   1 (default): the direct 3x3 kernel reads the operands of its next
  *                        half-step while the current one's MFMAs issue; 0: compiler schedule
  *   RR_TUNE_STEM         2 (default): fused stem v3 (pixels x channels MFMA, lane-local
- *                        pooling; 3 / 4: patch fill in 2 / 5 parts); 1: v2 (pools the raw
- *                        conv before BN/activation, exact by monotonicity); 0: v1 (BN/activation
- *                        on every stem pixel).  Odd stem maps always take v1.
+ *                        pooling; 3 / 4: patch fill in 2 / 5 parts; 6: the 3-part fill without
+ *                        border selects where a pixel pair lies inside the image); 5: v4
+ *                        (space-to-depth K: same value per tap as v3, another f32 summation
+ *                        order); 1: v2 (pools the raw conv before BN/activation, exact by
+ *                        monotonicity); 0: v1 (BN/activation on every stem pixel).  Odd stem
+ *                        maps always take v1.
  *   RR_TUNE_STREAM_XCD   1 (default): the streaming 1x1's channel-slice blocks of one pixel
  *                        strip run on one XCD (the strip's input is re-read from that L2)
  *   RR_TUNE_CONV3S       1 (default): the staggered two-wave-group direct 3x3 (persistent,
@@ -899,15 +916,25 @@ int rr_rank_full(const float* db_f32, long long n, const float* q_f32, int nq, i
  *                        c_out = 128 under RR_TUNE_CONV3X3 = 1; 2: also c_in = c_out = 64; 0 off
  *   RR_TUNE_WRES         1: the residual 256 -> 1024 / 512 -> 2048 1x1s (bottleneck conv3 of
  *                        mod4 / mod5) on the weight-stationary k_wres1x1 (weights in VGPRs,
- *                        activation + residual tiles by LDS-DMA); 2: also the non-residual
- *                        K = 256 / 512 1x1s (projections, strided or not; mod4 block-1 conv1;
- *                        default); 0: the streaming 1x1 / 8-phase GEMM
+ *                        activation + residual tiles by LDS-DMA); 2 (default): also the non-residual
+ *                        K = 256 / 512 1x1s (projections, strided or not; mod4 block-1 conv1);
+ *                        0: the streaming 1x1 / 8-phase GEMM
  *   RR_TUNE_PAIR_MID     1 (default): the 128/512 boundary of rr_conv1x1_pair on 32-pixel tiles
  *                        with a 4-slot residual ring (3 tiles ahead); 0: 64-pixel tiles, one ahead
  *                        (same results bit for bit)
  *   RR_TUNE_WRES_RING    1 (default): the non-residual k_wres1x1 forms (projections, mod4 block-1
  *                        conv1) keep 5 (K = 256) / 3 (K = 512) activation tiles in flight; 0: two
- *                        (same results bit for bit) */
+ *                        (same results bit for bit)
+ *
+ * Environment variables without a key (A/B switches, read where they apply):
+ *   RR_GEMM_PRIO=1       raised wave priority for the second half of k_igemm's waves
+ *   RR_GEMM8S_R=3|6      K-steps in flight per wave in k_gemm8s (default 4)
+ *   RR_GEMM_V1=1         the first-generation GEMM engine instead of the LDS-DMA engine
+ *   RR_KNN_SLAB_MB=n     kNN score-slab budget per GEMM pass, 16..1024 MiB (default 512)
+ *   RR_KNN_PREFIX=n      kNN chunks through the slab before the fused screen (default 4)
+ *   RR_KNN_TAU_MEMSET=1  reset the kNN running threshold by hipMemsetAsync, not a kernel
+ *   RR_KNN_CUT=0         no certified re-score cut in the kNN candidate select
+ *   RR_KNN_FSEL=0        the unstaged final kNN select */
 enum rr_tune_key { RR_TUNE_GEMM_CONFIG = 0, RR_TUNE_GEMM_STAGES = 1, RR_TUNE_GEMM_WIDE = 2,
                    RR_TUNE_GEMM_ASTAT = 3, RR_TUNE_GEMM_XCD_MAP = 4, RR_TUNE_STREAM_1X1 = 5,
                    RR_TUNE_CONV3X3 = 6, RR_TUNE_GRID_CUS = 7, RR_TUNE_GEMM8 = 8,
@@ -915,6 +942,7 @@ enum rr_tune_key { RR_TUNE_GEMM_CONFIG = 0, RR_TUNE_GEMM_STAGES = 1, RR_TUNE_GEM
                    RR_TUNE_STEM = 11, RR_TUNE_STREAM_XCD = 12, RR_TUNE_CONV3S = 13,
                    RR_TUNE_WRES = 14, RR_TUNE_PAIR_MID = 15, RR_TUNE_WRES_RING = 16 };
 int rr_set_tuning(int key, int value);
+int rr_get_tuning(int key, int* value);
 
 /* ----------------------------------------------------------- data helpers */
 /* Counter-based N(0,1) rows, each L2-normalised: row i of the global matrix

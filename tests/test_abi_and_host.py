@@ -2,9 +2,12 @@
 bound) and of the host-side mirror of the reference interface (no GPU
 compute calls here)."""
 
+import ctypes
+import json
 import os
 import re
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -225,3 +228,110 @@ def test_library_built_from_this_tree():
     assert info["source_digest"] == m.digest(), info
     # the Makefile's ARCH (gfx950 unless overridden) is recorded, not assumed
     assert info["arch"].startswith("gfx"), info
+
+
+# ------------------------------------------------------------------ tuning table
+TUNE_DEFAULTS = {0: 0, 1: 2, 2: 1, 3: 0, 4: 0, 5: 1, 6: 1, 7: 0, 8: 1, 9: 1, 10: 1, 11: 2, 12: 1, 13: 1, 14: 2,
+                 15: 1, 16: 1}
+TUNE_BOOL_KEYS = (2, 3, 4, 9)
+# (key, value set, value read back): every value a test or tool passes
+TUNE_ROUND_TRIPS = (
+    [(0, v, v) for v in range(9)] + [(1, 2, 2), (1, 3, 3), (1, 7, 2)] + [(5, v, v) for v in range(4)] +
+    [(6, v, v) for v in range(10)] + [(7, v, v) for v in (0, 8, 16)] +
+    [(8, v, v) for v in (0, 1, 2, 9, 1 | 16, 1 | 32, 1 | 4 | 64 | 128 | 512)] + [(8, -1, 0)] +
+    [(11, v, v) for v in range(7)] + [(13, v, v) for v in range(3)] + [(14, v, v) for v in range(3)] +
+    [(k, v, r) for k in TUNE_BOOL_KEYS + (10, 12, 15, 16) for v, r in ((0, 0), (1, 1))] +
+    [(k, 5, 1) for k in TUNE_BOOL_KEYS])
+
+
+def _tuning_in_fresh_process(**env):
+    """{key: rr_get_tuning(key)} of a new process whose environment has no RR_* variable but env."""
+    clean = {k: v for k, v in os.environ.items() if not k.startswith("RR_")}
+    clean.update(env)
+    code = ("import ctypes, json, sys; lib = ctypes.CDLL(sys.argv[1]); v = ctypes.c_int(); out = {}\n"
+            "for k in range(17):\n"
+            "    assert lib.rr_get_tuning(k, ctypes.byref(v)) == 0; out[k] = v.value\n"
+            "print(json.dumps(out))")
+    out = subprocess.run([sys.executable, "-c", code, LIB], env=clean, capture_output=True, text=True, check=True)
+    return {int(k): v for k, v in json.loads(out.stdout).items()}
+
+
+def test_tuning_key_constants_match_header():
+    from cirtorch import _engine as E
+    body = re.search(r"enum rr_tune_key \{(.*?)\};", open(HEADER).read(), re.S).group(1)
+    keys = {name: int(value) for name, value in re.findall(r"(RR_TUNE_\w+)\s*=\s*(\d+)", body)}
+    assert len(keys) == 17 and sorted(keys.values()) == list(range(17))
+    assert {"RR_TUNE_" + name: key for key, name in enumerate(E.TUNE_KEYS)} == keys
+    assert {name: getattr(E, name) for name in keys} == keys
+
+
+def test_tuning_defaults_in_fresh_process():
+    assert _tuning_in_fresh_process() == TUNE_DEFAULTS
+
+
+@pytest.mark.parametrize("env,key,value", [("RR_GEMM_STAGES", 1, 3), ("RR_GEMM_WIDE", 2, 0), ("RR_GEMM8", 8, 0),
+                                           ("RR_KNN_FUSED", 9, 0)])
+def test_tuning_seeded_from_environment(env, key, value):
+    assert _tuning_in_fresh_process(**{env: str(value)}) == {**TUNE_DEFAULTS, key: value}
+
+
+def test_tuning_set_get_round_trip():
+    from cirtorch import _engine as E
+    lib, got = E.lib(), ctypes.c_int()
+    start = {k: E.get_tuning(k) for k in range(17)}
+    try:
+        for key, value, back in TUNE_ROUND_TRIPS:
+            if key == E.RR_TUNE_KNN_FUSED and start[key] == 0:
+                continue  # RR_KNN_FUSED=0 in this process's environment pins the key
+            assert lib.rr_set_tuning(key, value) == 0, (key, value)
+            assert lib.rr_get_tuning(key, ctypes.byref(got)) == 0 and got.value == back, (key, value, got.value)
+            assert lib.rr_set_tuning(key, got.value) == 0                      # set(get) changes nothing
+            assert lib.rr_get_tuning(key, ctypes.byref(got)) == 0 and got.value == back, (key, value, got.value)
+    finally:
+        for key, value in start.items():
+            lib.rr_set_tuning(key, value)
+    assert {k: E.get_tuning(k) for k in range(17)} == start
+
+
+def test_tuning_errors_name_the_function():
+    from cirtorch import _engine as E
+    lib, got = E.lib(), ctypes.c_int()
+    for key in (-1, 17, 1 << 20):
+        assert lib.rr_set_tuning(key, 0) != 0 and b"rr_set_tuning" in lib.rr_last_error()
+        assert lib.rr_get_tuning(key, ctypes.byref(got)) != 0 and b"rr_get_tuning" in lib.rr_last_error()
+    assert lib.rr_get_tuning(0, None) != 0 and b"rr_get_tuning" in lib.rr_last_error()
+    assert lib.rr_set_tuning(E.RR_TUNE_GRID_CUS, -1) != 0 and b"RR_TUNE_GRID_CUS must be >= 0" in lib.rr_last_error()
+    with pytest.raises(ValueError, match="unknown tuning key"):
+        E.get_tuning("NO_SUCH_KEY")
+
+
+def test_tuning_context_manager_restores_state():
+    from cirtorch import _engine as E
+    start = {k: E.get_tuning(k) for k in range(17)}
+    with E.tuning(WRES=0, GEMM8=1 | 8, GRID_CUS=16):
+        assert (E.get_tuning("WRES"), E.get_tuning("GEMM8"), E.get_tuning("GRID_CUS")) == (0, 9, 16)
+        with E.tuning(WRES=1):
+            assert E.get_tuning(E.RR_TUNE_WRES) == 1
+        assert E.get_tuning("WRES") == 0
+    assert {k: E.get_tuning(k) for k in range(17)} == start
+    with pytest.raises(KeyError):
+        with E.tuning(STEM=5, CONV3X3=0):
+            assert (E.get_tuning("STEM"), E.get_tuning("CONV3X3")) == (5, 0)
+            raise KeyError("body")
+    assert {k: E.get_tuning(k) for k in range(17)} == start
+    with pytest.raises(RuntimeError, match="RR_TUNE_GRID_CUS"):  # a refused value: the keys set before it go back
+        with E.tuning(STEM=5, GRID_CUS=-1):
+            pass
+    assert {k: E.get_tuning(k) for k in range(17)} == start
+
+
+def test_apply_tuning_arg_takes_names_and_numbers():
+    from cirtorch import _engine as E
+    start = {k: E.get_tuning(k) for k in range(17)}
+    try:
+        E.apply_tuning_arg("WRES=0,rr_tune_stem=5, 8=0x9,")
+        assert (E.get_tuning("WRES"), E.get_tuning("STEM"), E.get_tuning("GEMM8")) == (0, 5, 9)
+        E.apply_tuning_arg("")
+    finally:
+        for key, value in start.items():
+            E.set_tuning(key, value)

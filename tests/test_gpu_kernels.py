@@ -53,11 +53,8 @@ def test_conv_tile_configs(cuda, cfg, case, prec):
     """Every forced tile configuration of the GEMM engine (rr_set_tuning) is
     exact on every conv shape — the automatic choice may pick any of them."""
     from cirtorch import _engine as E
-    E.check(E.lib().rr_set_tuning(0, cfg), "rr_set_tuning")
-    try:
+    with E.tuning(GEMM_CONFIG=cfg):
         _check_conv(cuda, case, prec, True)
-    finally:
-        E.lib().rr_set_tuning(0, 0)
 
 
 @pytest.mark.parametrize("cfg", [1, 2, 5])
@@ -66,13 +63,8 @@ def test_conv_tile_configs_3stage(cuda, cfg, case):
     """3-stage LDS ring (one barrier per K-step, refill issued after it) on the
     4-wave tiles: exact on every conv shape."""
     from cirtorch import _engine as E
-    E.check(E.lib().rr_set_tuning(0, cfg), "rr_set_tuning")
-    E.check(E.lib().rr_set_tuning(1, 3), "rr_set_tuning")
-    try:
+    with E.tuning(GEMM_CONFIG=cfg, GEMM_STAGES=3):
         _check_conv(cuda, case, "bf16", True)
-    finally:
-        E.lib().rr_set_tuning(0, 0)
-        E.lib().rr_set_tuning(1, 2)
 
 
 STREAM_CASES = [
@@ -98,13 +90,8 @@ def test_conv_stream1x1(cuda, case, mode, prec):
     """The weight-stationary streaming 1x1 kernel (mode 1) and the tiled engine
     (mode 0) on the same shapes."""
     from cirtorch import _engine as E
-    E.check(E.lib().rr_set_tuning(5, mode), "rr_set_tuning")
-    E.check(E.lib().rr_set_tuning(14, 0), "rr_set_tuning")  # the streaming kernel, not k_wres1x1
-    try:
+    with E.tuning(STREAM_1X1=mode, WRES=0):  # WRES 0: the streaming kernel, not k_wres1x1
         _check_conv(cuda, case, prec, True)
-    finally:
-        E.lib().rr_set_tuning(5, 1)
-        E.lib().rr_set_tuning(14, 2)
 
 
 XCD_CASES = [
@@ -121,14 +108,9 @@ def test_stream1x1_xcd_map(cuda, case):
     pure block-to-work remapping: exact vs float64, bit-identical to the plain order."""
     from cirtorch import _engine as E
     outs = []
-    E.check(E.lib().rr_set_tuning(14, 0), "rr_set_tuning")  # the streaming kernel, not k_wres1x1
-    try:
-        for xcd in (1, 0):
-            E.check(E.lib().rr_set_tuning(12, xcd), "rr_set_tuning")
+    for xcd in (1, 0):
+        with E.tuning(WRES=0, STREAM_XCD=xcd):  # WRES 0: the streaming kernel, not k_wres1x1
             outs.append(_check_conv(cuda, case, "bf16", True))
-    finally:
-        E.lib().rr_set_tuning(12, 1)
-        E.lib().rr_set_tuning(14, 2)
     assert torch.equal(outs[0], outs[1])
 
 
@@ -155,17 +137,12 @@ def test_wres1x1(cuda, case, prec):
     exact vs float64 and bit-identical to the streaming 1x1 (same K order)."""
     from cirtorch import _engine as E
     outs = []
-    try:
-        for on in (2, 0):
-            E.check(E.lib().rr_set_tuning(14, on), "rr_set_tuning")
+    for on in (2, 0):
+        with E.tuning(WRES=on):
             outs.append(_check_conv(cuda, case, prec, True))
-        # RR_TUNE_WRES_RING = 0: the non-residual forms two tiles ahead instead of 5 / 3
-        E.check(E.lib().rr_set_tuning(14, 2), "rr_set_tuning")
-        E.check(E.lib().rr_set_tuning(16, 0), "rr_set_tuning")
+    # RR_TUNE_WRES_RING = 0: the non-residual forms two tiles ahead instead of 5 / 3
+    with E.tuning(WRES=2, WRES_RING=0):
         outs.append(_check_conv(cuda, case, prec, True))
-    finally:
-        E.lib().rr_set_tuning(14, 2)
-        E.lib().rr_set_tuning(16, 1)
     assert torch.equal(outs[0], outs[1])
     assert torch.equal(outs[0], outs[2])
 
@@ -184,12 +161,9 @@ def test_c3w64_bit_identical(cuda, case, prec):
     bit-identical to the A-stationary direct kernel (same (tap, half-step) order)."""
     from cirtorch import _engine as E
     outs = []
-    try:
-        for mode in (9, 4):
-            E.check(E.lib().rr_set_tuning(6, mode), "rr_set_tuning")
+    for mode in (9, 4):
+        with E.tuning(CONV3X3=mode):
             outs.append(_check_conv(cuda, case, prec, True))
-    finally:
-        E.lib().rr_set_tuning(6, 1)
     assert torch.equal(outs[0], outs[1])
 
 
@@ -212,11 +186,8 @@ def test_conv3x3_direct(cuda, case, mode, prec):
     """Direct 3x3 kernel (modes 1-4, 6: auto / 8x32 / 4x32 tiles / A-stationary wave layouts) and the
     implicit-GEMM fallback (mode 0) against the float64 reference."""
     from cirtorch import _engine as E
-    E.check(E.lib().rr_set_tuning(6, mode), "rr_set_tuning")
-    try:
+    with E.tuning(CONV3X3=mode):
         _check_conv(cuda, case, prec, True)
-    finally:
-        E.lib().rr_set_tuning(6, 1)
 
 
 @pytest.mark.parametrize("prec", ["bf16", "fp16"])
@@ -227,12 +198,9 @@ def test_conv3x3_pipelined_schedule_bit_identical(cuda, prec):
     from cirtorch import _engine as E
     case = (3, 64, 24, 96, 64, 3, 1, 1, False, True)
     outs = []
-    try:
-        for pipe in (0, 1):
-            E.check(E.lib().rr_set_tuning(10, pipe), "rr_set_tuning")
+    for pipe in (0, 1):
+        with E.tuning(CONV3_PIPE=pipe):
             outs.append(_check_conv(cuda, case, prec, True))
-    finally:
-        E.lib().rr_set_tuning(10, 1)
     assert torch.equal(outs[0], outs[1])
 
 
@@ -258,15 +226,10 @@ def test_conv3s_staggered(cuda, case, cap, prec):
     so it is also bit-identical to it."""
     from cirtorch import _engine as E
     outs = []
-    try:
-        E.check(E.lib().rr_set_tuning(7, cap), "rr_set_tuning")
-        # 2: both forms (the c_in = c_out = 64 one is opt-in), 1: default, 0: k_conv3x3
-        for on in (2, 1, 0):
-            E.check(E.lib().rr_set_tuning(13, on), "rr_set_tuning")
+    # 2: both forms (the c_in = c_out = 64 one is opt-in), 1: default, 0: k_conv3x3
+    for on in (2, 1, 0):
+        with E.tuning(GRID_CUS=cap, CONV3S=on):
             outs.append(_check_conv(cuda, case, prec, True))
-    finally:
-        E.lib().rr_set_tuning(13, 1)
-        E.lib().rr_set_tuning(7, 0)
     # the c_out = 128 form accumulates in k_conv3x3's (chunk, tap, half-step) order
     if case[4] == 128:
         assert torch.equal(outs[0], outs[2]) and torch.equal(outs[1], outs[2])
@@ -462,13 +425,10 @@ def test_stem_pool_before_epilogue_bit_identical(cuda, dt, shape):
     wpk = ops.pack_stem_weights(wt.to(cuda), dt)
     xu = (x * 255).to(torch.uint8)
     outs = {}
-    try:
-        for mode in (0, 1, 2, 3, 4, 6):
-            E.check(E.lib().rr_set_tuning(11, mode), "rr_set_tuning")
+    for mode in (0, 1, 2, 3, 4, 6):
+        with E.tuning(STEM=mode):
             outs[mode] = [ops.stem_conv_pool(inp.to(cuda), wpk, scale.to(cuda), shift.to(cuda), leaky=True,
                                              slope=0.01, mean=mean, std=std).float().cpu() for inp in (x, xu)]
-    finally:
-        E.lib().rr_set_tuning(11, 2)
     neg = scale < 0
     ulp = 2.0 ** -7 if dt == torch.bfloat16 else 2.0 ** -10
     for a, b in zip(outs[0], outs[1]):
@@ -592,13 +552,10 @@ def test_conv1x1_pair_mod3_ring_equals_64px_kernel(cuda, dt, shape):
     more than 2^20 pixels (two chunk launches)."""
     from cirtorch import _engine as E
     n, h, w = shape
-    try:
-        E.check(E.lib().rr_set_tuning(15, 0), "rr_set_tuning")
+    with E.tuning(PAIR_MID=0):
         y0, z0, _, _ = _mod3_pair_case(dt, n, h, w, 3 * h + w, cuda, ref=False)
-        E.check(E.lib().rr_set_tuning(15, 1), "rr_set_tuning")
+    with E.tuning(PAIR_MID=1):
         y1, z1, _, _ = _mod3_pair_case(dt, n, h, w, 3 * h + w, cuda, ref=False)
-    finally:
-        E.lib().rr_set_tuning(15, 1)
     assert torch.equal(y0, y1)
     assert torch.equal(z0, z1)
 
@@ -691,18 +648,11 @@ GEMM8_CASES = [
 @pytest.mark.parametrize("prec", ["bf16", "fp16"])
 @pytest.mark.parametrize("perm", [True, False])
 def test_gemm8_forced_vs_float64(cuda, case, prec, perm):
-    """The 8-phase staggered 256x256 GEMM (rr_set_tuning(RR_TUNE_GEMM8, 2):
+    """The 8-phase staggered 256x256 GEMM (RR_TUNE_GEMM8 = 2:
     forced wherever structurally legal) against the float64 reference."""
     from cirtorch import _engine as E
-    E.check(E.lib().rr_set_tuning(8, 2), "rr_set_tuning")
-    E.check(E.lib().rr_set_tuning(6, 0), "rr_set_tuning")   # no direct 3x3 kernel
-    E.check(E.lib().rr_set_tuning(5, 0), "rr_set_tuning")   # no streaming 1x1 kernel
-    try:
+    with E.tuning(GEMM8=2, CONV3X3=0, STREAM_1X1=0):  # no direct 3x3, no streaming 1x1 kernel
         _check_conv(cuda, case, prec, perm)
-    finally:
-        E.lib().rr_set_tuning(8, 1)
-        E.lib().rr_set_tuning(6, 1)
-        E.lib().rr_set_tuning(5, 1)
 
 
 @pytest.mark.parametrize("shape", [(128, 48, 64, 1024, 256, 1, 1), (128, 24, 32, 2048, 512, 1, 1),
@@ -722,17 +672,10 @@ def test_gemm8_bit_identical_to_tiled_engine(cuda, shape, prec):
     sc = torch.rand(cout, generator=g, device=cuda) + 0.5
     sh = torch.randn(cout, generator=g, device=cuda) * 0.1
     p = 1 if k == 3 else 0
-    E.check(E.lib().rr_set_tuning(6, 0), "rr_set_tuning")
-    E.check(E.lib().rr_set_tuning(5, 0), "rr_set_tuning")
-    E.check(E.lib().rr_set_tuning(8, 2), "rr_set_tuning")
-    try:
+    with E.tuning(CONV3X3=0, STREAM_1X1=0, GEMM8=2):
         a = _ops().conv2d_fused(x, wp, k, k, s, p, cout, sc, sh, leaky=True, perm32=True)
-        E.check(E.lib().rr_set_tuning(8, 0), "rr_set_tuning")
+    with E.tuning(CONV3X3=0, STREAM_1X1=0, GEMM8=0):
         b = _ops().conv2d_fused(x, wp, k, k, s, p, cout, sc, sh, leaky=True, perm32=True)
-    finally:
-        E.lib().rr_set_tuning(8, 1)
-        E.lib().rr_set_tuning(6, 1)
-        E.lib().rr_set_tuning(5, 1)
     assert torch.equal(a, b)
 
 
@@ -754,17 +697,10 @@ def test_gemm8_residual_epilogue_bit_identical(cuda, shape, leaky, prec):
     sc[::7] *= -1.0
     sh = torch.randn(cout, generator=g, device=cuda) * 0.1
     res = torch.randn((n, h, w, cout), generator=g, device=cuda).to(dt)
-    E.check(E.lib().rr_set_tuning(6, 0), "rr_set_tuning")
-    E.check(E.lib().rr_set_tuning(5, 0), "rr_set_tuning")
-    try:
-        E.check(E.lib().rr_set_tuning(8, 2), "rr_set_tuning")
+    with E.tuning(CONV3X3=0, STREAM_1X1=0, GEMM8=2):
         a = _ops().conv2d_fused(x, wp, 1, 1, 1, 0, cout, sc, sh, residual=res, leaky=leaky, perm32=True)
-        E.check(E.lib().rr_set_tuning(8, 0), "rr_set_tuning")
+    with E.tuning(CONV3X3=0, STREAM_1X1=0, GEMM8=0):
         b = _ops().conv2d_fused(x, wp, 1, 1, 1, 0, cout, sc, sh, residual=res, leaky=leaky, perm32=True)
-    finally:
-        E.lib().rr_set_tuning(8, 1)
-        E.lib().rr_set_tuning(6, 1)
-        E.lib().rr_set_tuning(5, 1)
     assert torch.equal(a, b)
 
 
@@ -790,19 +726,10 @@ def test_gemm8_persistent_equals_one_block_per_tile(cuda, shape, cap, resid):
     if resid and k != 1:
         pytest.skip("residual epilogues are 1x1s")
     res = torch.randn((n, h, w, cout), generator=g, device=cuda).to(torch.bfloat16) if resid else None
-    E.check(E.lib().rr_set_tuning(6, 0), "rr_set_tuning")
-    E.check(E.lib().rr_set_tuning(5, 0), "rr_set_tuning")
-    try:
-        E.check(E.lib().rr_set_tuning(8, 2 | 4), "rr_set_tuning")
+    with E.tuning(CONV3X3=0, STREAM_1X1=0, GEMM8=2 | 4):
         ref = _ops().conv2d_fused(x, wp, k, k, s, p, cout, sc, sh, residual=res, leaky=True, perm32=True)
-        E.check(E.lib().rr_set_tuning(8, 2), "rr_set_tuning")
-        E.check(E.lib().rr_set_tuning(7, cap), "rr_set_tuning")
+    with E.tuning(CONV3X3=0, STREAM_1X1=0, GEMM8=2, GRID_CUS=cap):
         got = _ops().conv2d_fused(x, wp, k, k, s, p, cout, sc, sh, residual=res, leaky=True, perm32=True)
-    finally:
-        E.lib().rr_set_tuning(7, 0)
-        E.lib().rr_set_tuning(8, 1)
-        E.lib().rr_set_tuning(6, 1)
-        E.lib().rr_set_tuning(5, 1)
     assert torch.equal(got, ref)
 
 
@@ -825,24 +752,16 @@ def test_gemm8a_bit_identical_to_tiled_engine(cuda, shape, prec):
     wp = _ops().pack_conv_weights(wt, cin, dt, perm32=True)
     sc = torch.rand(cout, generator=g, device=cuda) + 0.5
     sh = torch.randn(cout, generator=g, device=cuda) * 0.1
-    E.check(E.lib().rr_set_tuning(6, 0), "rr_set_tuning")
-    E.check(E.lib().rr_set_tuning(5, 0), "rr_set_tuning")
-    try:
+    with E.tuning(CONV3X3=0, STREAM_1X1=0):
         a = _ops().conv2d_fused(x, wp, k, k, s, 1, cout, sc, sh, leaky=True, perm32=True)
-        E.check(E.lib().rr_set_tuning(8, 1 | 128), "rr_set_tuning")  # one block per tile
-        c = _ops().conv2d_fused(x, wp, k, k, s, 1, cout, sc, sh, leaky=True, perm32=True)
-        E.check(E.lib().rr_set_tuning(8, 1 | 16), "rr_set_tuning")
-        b = _ops().conv2d_fused(x, wp, k, k, s, 1, cout, sc, sh, leaky=True, perm32=True)
+        with E.tuning(GEMM8=1 | 128):  # one block per tile
+            c = _ops().conv2d_fused(x, wp, k, k, s, 1, cout, sc, sh, leaky=True, perm32=True)
+        with E.tuning(GEMM8=1 | 16):
+            b = _ops().conv2d_fused(x, wp, k, k, s, 1, cout, sc, sh, leaky=True, perm32=True)
         # a grid capped below the 8 XCDs (RR_TUNE_GRID_CUS = 4): one block per tile then
         # (the persistent grid left XCDs 4..7's tile ranges unwritten)
-        E.check(E.lib().rr_set_tuning(8, 1), "rr_set_tuning")
-        E.check(E.lib().rr_set_tuning(7, 4), "rr_set_tuning")
-        d = _ops().conv2d_fused(x, wp, k, k, s, 1, cout, sc, sh, leaky=True, perm32=True)
-    finally:
-        E.lib().rr_set_tuning(7, 0)
-        E.lib().rr_set_tuning(8, 1)
-        E.lib().rr_set_tuning(6, 1)
-        E.lib().rr_set_tuning(5, 1)
+        with E.tuning(GEMM8=1, GRID_CUS=4):
+            d = _ops().conv2d_fused(x, wp, k, k, s, 1, cout, sc, sh, leaky=True, perm32=True)
     assert torch.equal(a, b)
     assert torch.equal(a, c)
     assert torch.equal(a, d)
@@ -867,21 +786,13 @@ def test_every_3x3_path_same_bits(cuda, case, prec):
     the output bits are the same: direct kernels, the 8-phase GEMMs and the tiled
     engine on tap-uniform im2col."""
     from cirtorch import _engine as E
-    L = E.lib()
     outs = {}
     # (RR_TUNE_CONV3X3, RR_TUNE_GEMM8, RR_TUNE_GRID_CUS): a CU cap of 8 makes the
     # 8-phase kernels eligible on these small problems
     paths = {"direct": (1, 0, 0), "gemm8": (0, 2, 8), "gemm8a": (0, 1 | 4, 8), "tiled": (0, 0, 0)}
-    try:
-        for name, (c3, g8, cap) in paths.items():
-            E.check(L.rr_set_tuning(6, c3), "rr_set_tuning")
-            E.check(L.rr_set_tuning(8, g8), "rr_set_tuning")
-            E.check(L.rr_set_tuning(7, cap), "rr_set_tuning")
+    for name, (c3, g8, cap) in paths.items():
+        with E.tuning(CONV3X3=c3, GEMM8=g8, GRID_CUS=cap):
             outs[name] = _check_conv(cuda, case, prec, True)
-    finally:
-        L.rr_set_tuning(6, 1)
-        L.rr_set_tuning(8, 1)
-        L.rr_set_tuning(7, 0)
     ref = outs.pop("tiled")
     for name, o in outs.items():
         assert torch.equal(o, ref), name

@@ -269,11 +269,8 @@ def _fused_vs_slab(cuda, db, qq, k, prec):
     index = KnnIndex(torch.from_numpy(db).to(cuda), prec)
     q = torch.from_numpy(qq).to(cuda)
     s1, i1 = index.search(q, k, verify=False)
-    E.check(E.lib().rr_set_tuning(9, 0), "rr_set_tuning")
-    try:
+    with E.tuning(KNN_FUSED=0):
         s0, i0 = index.search(q, k, verify=False)
-    finally:
-        E.lib().rr_set_tuning(9, 1)
     return (s1.cpu().numpy(), i1.cpu().numpy()), (s0.cpu().numpy(), i0.cpu().numpy())
 
 
@@ -453,7 +450,7 @@ def test_knn_verify_tight_cluster(cuda, prec):
 def test_knn_half_width_gemm_equals_tiled(cuda, prec, nq):
     """<= 128 queries: the score GEMM on k_gemm8h (256 database rows x 128
     queries, 8-phase staggered, 3-stage ring) vs the tiled engine
-    (rr_set_tuning(RR_TUNE_GEMM8, 1 | 8)): identical top-k indices and exact
+    (RR_TUNE_GEMM8 = 1 | 8): identical top-k indices and exact
     float64 scores, over the prefix slab and the fused screen (n = 300k rows,
     a ragged last database tile)."""
     from cirtorch import _engine as E
@@ -462,12 +459,9 @@ def test_knn_half_width_gemm_equals_tiled(cuda, prec, nq):
     db = _ops.fill_unit_rows(300_001, 2048, seed=0x5EED8, device=cuda)
     q = _ops.fill_unit_rows(nq, 2048, seed=0x5EED9 + nq, device=cuda)
     out = {}
-    try:
-        for v in (1, 9):
-            E.check(E.lib().rr_set_tuning(8, v), "rr_set_tuning")
+    for v in (1, 9):
+        with E.tuning(GEMM8=v):
             out[v] = KnnIndex(db, prec).search(q, 100, verify=False)
-    finally:
-        E.lib().rr_set_tuning(8, 1)
     assert torch.equal(out[1][1], out[9][1])
     assert torch.equal(out[1][0], out[9][0])
 

@@ -255,13 +255,9 @@ def test_batch_invariant_descriptors(cuda, precision):
     net = random_init_(make_net("resnet50", precision=precision, mean=mean, std=std), 6).to(cuda).eval()
     g = torch.Generator().manual_seed(2)
     x = torch.randint(0, 256, (8, 3, 768, 1024), generator=g, dtype=torch.uint8).to(cuda)
-    try:
-        E.check(E.lib().rr_set_tuning(7, 16), "rr_set_tuning")
-        with torch.no_grad():
-            many = net.extract(x)
-            one = net.extract(x[3:4].clone())
-    finally:
-        E.lib().rr_set_tuning(7, 0)
+    with E.tuning(GRID_CUS=16), torch.no_grad():
+        many = net.extract(x)
+        one = net.extract(x[3:4].clone())
     assert torch.equal(many[:, 3:4], one)
 
 
@@ -277,9 +273,6 @@ def test_search_with_capped_grid_equals_full_grid(cuda, nq, cap):
     q = _unit_rows(nq, 2048, seed=32).to(cuda)
     idx = KnnIndex(db, "bf16")
     s0, i0 = idx.search(q, 50, verify=False)
-    E.check(E.lib().rr_set_tuning(7, cap), "rr_set_tuning")
-    try:
+    with E.tuning(GRID_CUS=cap):
         s1, i1 = idx.search(q, 50, verify=False)
-    finally:
-        E.lib().rr_set_tuning(7, 0)
     assert torch.equal(i0, i1) and torch.equal(s0, s1)

@@ -278,9 +278,8 @@ def test_stem_v4_space_to_depth(cuda, dt, shape):
     xu = (x * 255).to(torch.uint8)
     xf = xu.float() / 255.0
     outs = {}
-    try:
-        for mode in (2, 5):
-            E.check(E.lib().rr_set_tuning(11, mode), "rr_set_tuning")
+    for mode in (2, 5):
+        with E.tuning(STEM=mode):
             outs[mode] = [ops.stem_conv_pool(inp.to(cuda), wpk, scale.to(cuda), shift.to(cuda), leaky=True, slope=0.01,
                                              mean=MEAN, std=STD).float().cpu() for inp in (xf, xu)]
             if mode == 5:
@@ -291,8 +290,6 @@ def test_stem_v4_space_to_depth(cuda, dt, shape):
                     pad[i, :, : h - 2 * i, : w - 4 * i] = xu[i, :, : h - 2 * i, : w - 4 * i]
                 ref_rag = ops.stem_conv_pool(pad.to(cuda), wpk, scale.to(cuda), shift.to(cuda), mean=MEAN, std=STD)
                 assert torch.equal(rag, ref_rag)
-    finally:
-        E.lib().rr_set_tuning(11, 2)
     v3, v4 = outs[2][0], outs[5][0]
     assert torch.equal(outs[5][0], outs[5][1])            # uint8 == float x / 255
     xn = ((xf - torch.tensor(MEAN)[:, None, None]) / torch.tensor(STD)[:, None, None]).to(dt).float()

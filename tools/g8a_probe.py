@@ -20,20 +20,19 @@ def main():
     sc, sh = torch.ones(128, device="cuda"), torch.zeros(128, device="cuda")
     outs = {}
     for name, v in (("persistent", 1), ("per-tile", 1 | 128), ("persistent", 1)):
-        E.check(E.lib().rr_set_tuning(8, v), "rr_set_tuning")
         f = lambda: ops.conv2d_fused(x, wp, 3, 3, 2, 1, 128, sc, sh, leaky=True, perm32=True)  # noqa: E731
-        for _ in range(3):
-            y = f()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(10):
-            y = f()
-        e1.record()
-        torch.cuda.synchronize()
+        with E.tuning(GEMM8=v):
+            for _ in range(3):
+                y = f()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(10):
+                y = f()
+            e1.record()
+            torch.cuda.synchronize()
         outs.setdefault(name, y)
         print("gemm8a %-10s n=%d: %.1f us" % (name, n, e0.elapsed_time(e1) / 10 * 1e3), flush=True)
-    E.lib().rr_set_tuning(8, 1)
     print("bit-identical:", torch.equal(outs["persistent"], outs["per-tile"]))
 
 

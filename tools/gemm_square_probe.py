@@ -27,7 +27,7 @@ def main():
     from cirtorch import _ops as ops
     from cirtorch import _engine as E
     if os.environ.get("G8"):  # RR_TUNE_GEMM8 value (2: k_gemm8 wherever legal, persistent)
-        E.check(E.lib().rr_set_tuning(8, int(os.environ["G8"])), "rr_set_tuning")
+        E.set_tuning("GEMM8", int(os.environ["G8"]))
     dt = torch.float16
     g = torch.Generator(device="cuda").manual_seed(1)
     shapes = ((4096, 4096, 4096), (8192, 8192, 8192), (16384, 4096, 2048), (393216, 256, 1024), (131072, 1024, 2048))

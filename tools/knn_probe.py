@@ -15,16 +15,14 @@ def main():
     ap.add_argument("--q", type=int, default=128)
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--tune", default="", help="rr_set_tuning pairs key=value[,key=value]")
+    ap.add_argument("--tune", default="", help="tuning pairs key=value[,key=value], keys by name or number")
     ap.add_argument("--screen", default="fp16", help="screening dtype (int8 / fp16 / bf16 / fp32)")
     ap.add_argument("--no-verify", dest="verify", action="store_false",
                     help="unverified search (default: the bench's certified search, certificate resolved)")
     args = ap.parse_args()
     from cirtorch import _ops
     from cirtorch import _engine as E
-    for kv in filter(None, args.tune.split(",")):
-        k_, v_ = kv.split("=")
-        E.check(E.lib().rr_set_tuning(int(k_), int(v_)), "rr_set_tuning")
+    E.apply_tuning_arg(args.tune)
     from cirtorch.search import KnnIndex
     db = _ops.fill_unit_rows(args.n, 2048, seed=0xDB5EED)
     q = _ops.fill_unit_rows(args.q, 2048, seed=0x0E5EED)

@@ -41,7 +41,7 @@ def main():
         lab8.lab_g8.restype = ctypes.c_int
         lab8.lab_g8.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 4 + [ctypes.c_void_p]
     if os.environ.get("G8"):
-        E.check(E.lib().rr_set_tuning(8, int(os.environ["G8"])), "rr_set_tuning")
+        E.set_tuning("GEMM8", int(os.environ["G8"]))
     variants = [int(v) for v in os.environ.get("VARIANTS", "0").split(",") if v]
     shapes = ((16384, 4096, 2048), (8192, 8192, 8192), (131072, 1024, 2048), (393216, 256, 1024),
               (100352, 2048, 512))

@@ -45,7 +45,7 @@ def main():
     ap.add_argument("--layer", default="mod2.b1.c2")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--tune", default="", help="key=value,... passed to rr_set_tuning")
+    ap.add_argument("--tune", default="", help="tuning pairs key=value[,key=value], keys by name or number")
     args = ap.parse_args()
     from cirtorch import _engine as E
     from cirtorch.backbones import resnet
@@ -57,9 +57,7 @@ def main():
     x = torch.rand(args.batch, 3, 768, 1024, device="cuda")
     calls = {n: (i, s, r) for n, i, s, r in walk(body, x)}
     inp, st, res = calls[args.layer]
-    for kv in filter(None, args.tune.split(",")):
-        k, v = kv.split("=")
-        E.check(E.lib().rr_set_tuning(int(k), int(v)), "rr_set_tuning")
+    E.apply_tuning_arg(args.tune)
     torch.cuda.synchronize()
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()

@@ -43,14 +43,11 @@ def main():
     p = n * h * w
     gb = p * 2 * (128 + 512 + 512 + 128) / 1e9
     out, t = {}, {0: [], 1: []}
-    try:
-        for rnd in range(3):
-            for mode in (0, 1):
-                E.check(E.lib().rr_set_tuning(15, mode), "rr_set_tuning")
+    for rnd in range(3):
+        for mode in (0, 1):
+            with E.tuning(PAIR_MID=mode):
                 out[mode] = run()
                 t[mode].append(timed(run))
-    finally:
-        E.lib().rr_set_tuning(15, 1)
     same = torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1])
     for mode in (0, 1):
         best = min(t[mode])

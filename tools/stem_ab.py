@@ -42,18 +42,17 @@ def main():
     res = {m: {"f32": [], "u8": []} for m in modes}
     outs = {}
     ea, eb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    try:
-        # warm-up of every mode and input first: the first timed loop of a process
-        # otherwise runs ~15 % slow (clocks / first touch), whichever mode it is
-        for m in modes:
-            E.check(E.lib().rr_set_tuning(11, m), "rr_set_tuning")
+    # warm-up of every mode and input first: the first timed loop of a process
+    # otherwise runs ~15 % slow (clocks / first touch), whichever mode it is
+    for m in modes:
+        with E.tuning(STEM=m):
             for inp in (x, xu):
                 for _ in range(5):
                     _ops.stem_conv_pool(inp, wpk, scale, shift, mean=mean, std=std)
-        torch.cuda.synchronize()
-        for rnd in range(args.rounds):
-            for m in modes:
-                E.check(E.lib().rr_set_tuning(11, m), "rr_set_tuning")
+    torch.cuda.synchronize()
+    for rnd in range(args.rounds):
+        for m in modes:
+            with E.tuning(STEM=m):
                 for name, inp in (("f32", x), ("u8", xu)):
                     y = _ops.stem_conv_pool(inp, wpk, scale, shift, mean=mean, std=std)
                     torch.cuda.synchronize()
@@ -65,8 +64,6 @@ def main():
                     res[m][name].append(ea.elapsed_time(eb) / args.reps * 1e3)
                     if rnd == 0:
                         outs[(m, name)] = y.float()
-    finally:
-        E.lib().rr_set_tuning(11, 2)
     cmp = {}
     for m in modes[1:]:
         for name in ("f32", "u8"):

@@ -39,14 +39,11 @@ def main():
         sc, sh = torch.ones(cout, device="cuda"), torch.zeros(cout, device="cuda")
         f = lambda: ops.conv2d_fused(x, wp, 1, 1, stride, 0, cout, sc, sh, leaky=True, perm32=True)  # noqa: E731
         t, out = {0: [], 1: []}, {}
-        try:
-            for _ in range(3):
-                for mode in (0, 1):
-                    E.check(E.lib().rr_set_tuning(16, mode), "rr_set_tuning")
+        for _ in range(3):
+            for mode in (0, 1):
+                with E.tuning(WRES_RING=mode):
                     out[mode] = f()
                     t[mode].append(timed(f))
-        finally:
-            E.lib().rr_set_tuning(16, 1)
         print("%-24s two ahead %s | deep %s us, bit-identical %s" % (
             name, " ".join("%.1f" % v for v in t[0]), " ".join("%.1f" % v for v in t[1]),
             torch.equal(out[0], out[1])), flush=True)
