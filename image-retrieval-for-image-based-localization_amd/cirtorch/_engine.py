@@ -25,6 +25,7 @@ RR_CONV_AFFINE, RR_CONV_RESIDUAL, RR_CONV_PERM32 = 1, 2, 4
 RR_NHWC, RR_NCHW = 0, 1
 RR_MATCH_NN, RR_MATCH_MNN, RR_MATCH_SNN, RR_MATCH_SMNN = 0, 1, 2, 3
 RR_RESP_HARRIS, RR_RESP_GFTT, RR_RESP_HESSIAN, RR_RESP_DOG = 0, 1, 2, 3
+RR_EPI_SAMPSON, RR_EPI_SYMMETRICAL = 0, 1
 # enum rr_tune_key, in order: RR_TUNE_<name> = index
 TUNE_KEYS = ("GEMM_CONFIG", "GEMM_STAGES", "GEMM_WIDE", "GEMM_ASTAT", "GEMM_XCD_MAP", "STREAM_1X1", "CONV3X3",
              "GRID_CUS", "GEMM8", "KNN_FUSED", "CONV3_PIPE", "STEM", "STREAM_XCD", "CONV3S", "WRES", "PAIR_MID",
@@ -100,6 +101,11 @@ _SIGS = {
     "rr_verify_pairs": ([_vp, _vp, _ll, _vp, _vp, _ll, _vp, _i, _i, _d, _i, _i, ctypes.c_ulonglong, _vp, _vp, _vp, _vp, _sz,
                          _vp], _i),
     "rr_homography_dlt": ([_vp, _vp, _vp, _vp, _ll, _i, _vp, _vp, _sz, _vp], _i),
+    "rr_verify_epipolar_workspace_bytes": ([_ll, _i, _i], _sz),
+    "rr_verify_pairs_epipolar": ([_vp, _vp, _ll, _vp, _vp, _ll, _vp, _i, _i, _d, _i, _i, ctypes.c_ulonglong, _vp, _vp, _vp,
+                                  _vp, _sz, _vp], _i),
+    "rr_fundamental_dlt": ([_vp, _vp, _vp, _vp, _ll, _i, _vp, _vp, _sz, _vp], _i),
+    "rr_epipolar_distance": ([_vp, _vp, _vp, _vp, _ll, _i, _i, _i, _d, _vp, _vp], _i),
     "rr_detect_workspace_bytes": ([_i, _i, _i, _i], _sz),
     "rr_response": ([_vp, _i, _i, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp], _i),
     "rr_nms2d": ([_vp, _ll, _i, _i, _i, _i, _vp, _vp], _i),

@@ -706,11 +706,17 @@ def match_pairs(a, a_off, b, b_off, mode, th=0.8, max_n1=None, max_n2=None, cove
 
 
 # ---------------------------------------------------------------- spatial verification
-def verify_pairs(kp1, off1, kp2, off2, match, th=3.0, iters=1024, refine=2, seed=0, max_n1=None, covered=False):
-    """rr_verify_pairs: kp1 [rows1, 2], kp2 [rows2, 2] float32 pixel keypoints, device int64 offsets
-    [P + 1], match int64 [rows1] (rr_match_pairs' output) -> (inliers int32 [P], H float64 [P, 3, 3],
-    mask uint8 [rows1]).  covered=True: the pairs cover every side-1 row (the mask is not
-    pre-filled with 0).  No synchronisation."""
+VERIFY_MODELS = {"homography": ("rr_verify_workspace_bytes", "rr_verify_pairs"),
+                 "fundamental": ("rr_verify_epipolar_workspace_bytes", "rr_verify_pairs_epipolar")}
+
+
+def verify_pairs(kp1, off1, kp2, off2, match, th=3.0, iters=1024, refine=2, seed=0, max_n1=None, covered=False,
+                 model="homography"):
+    """rr_verify_pairs (model "homography") / rr_verify_pairs_epipolar ("fundamental"): kp1 [rows1, 2],
+    kp2 [rows2, 2] float32 pixel keypoints, device int64 offsets [P + 1], match int64 [rows1]
+    (rr_match_pairs' output) -> (inliers int32 [P], H or F float64 [P, 3, 3], mask uint8 [rows1]).
+    covered=True: the pairs cover every side-1 row (the mask is not pre-filled with 0).  No synchronisation."""
+    ws_bytes, entry = VERIFY_MODELS[model]
     E.require_gpu(kp1, off1, kp2, off2, match)
     if kp1.dim() != 2 or kp2.dim() != 2 or kp1.shape[1] != 2 or kp2.shape[1] != 2:
         raise RuntimeError("verify: keypoints must be [rows, 2], got %s and %s" % (tuple(kp1.shape), tuple(kp2.shape)))
@@ -726,11 +732,11 @@ def verify_pairs(kp1, off1, kp2, off2, match, th=3.0, iters=1024, refine=2, seed
     inliers = torch.empty(npairs, dtype=torch.int32, device=dev)   # written for every pair
     H = torch.empty((npairs, 3, 3), dtype=torch.float64, device=dev)
     mask = (torch.empty if covered and npairs else torch.zeros)(rows1, dtype=torch.uint8, device=dev)
-    ws = _workspace(E.lib().rr_verify_workspace_bytes(rows1, npairs, int(iters)), dev)
-    E.check(E.lib().rr_verify_pairs(E.ptr(kp1), E.ptr(off1), rows1, E.ptr(kp2), E.ptr(off2), rows2, E.ptr(match),
+    ws = _workspace(getattr(E.lib(), ws_bytes)(rows1, npairs, int(iters)), dev)
+    E.check(getattr(E.lib(), entry)(E.ptr(kp1), E.ptr(off1), rows1, E.ptr(kp2), E.ptr(off2), rows2, E.ptr(match),
                                     npairs, max_n1, float(th), int(iters), int(refine),
                                     int(seed) & 0xFFFFFFFFFFFFFFFF, E.ptr(inliers), E.ptr(H), E.ptr(mask), E.ptr(ws),
-                                    ws.numel(), _st()), "rr_verify_pairs")
+                                    ws.numel(), _st()), entry)
     return inliers, H, mask
 
 
@@ -752,6 +758,47 @@ def homography_dlt(pts1, pts2, weights, off):
     E.check(E.lib().rr_homography_dlt(E.ptr(pts1), E.ptr(pts2), E.ptr(weights), E.ptr(off), rows, npairs, E.ptr(H),
                                       E.ptr(None), 0, _st()), "rr_homography_dlt")
     return H
+
+
+def fundamental_dlt(pts1, pts2, weights, off):
+    """rr_fundamental_dlt: the arguments of homography_dlt -> F float64 [P, 3, 3] (find_fundamental
+    per point set; zeros for a set of fewer than 8 points).  No synchronisation."""
+    E.require_gpu(pts1, pts2, weights, off)
+    if pts1.dim() != 2 or pts1.shape[1] != 2 or pts1.shape != pts2.shape:
+        raise RuntimeError("fundamental: points must be [rows, 2] on both sides, got %s and %s" % (tuple(pts1.shape), tuple(pts2.shape)))
+    if pts1.dtype != torch.float64 or pts2.dtype != torch.float64 or not pts1.is_contiguous() or not pts2.is_contiguous():
+        raise RuntimeError("fundamental: points must be contiguous float64 rows")
+    rows = pts1.shape[0]
+    if weights is not None and (weights.dtype != torch.float64 or weights.shape != (rows,) or not weights.is_contiguous()):
+        raise RuntimeError("fundamental: weights must be contiguous float64 [rows]")
+    if off.dtype != torch.int64 or off.numel() < 1:
+        raise RuntimeError("fundamental: offsets must be int64 [P + 1]")
+    npairs = off.numel() - 1
+    F = torch.empty((npairs, 3, 3), dtype=torch.float64, device=pts1.device)
+    E.check(E.lib().rr_fundamental_dlt(E.ptr(pts1), E.ptr(pts2), E.ptr(weights), E.ptr(off), rows, npairs, E.ptr(F),
+                                       E.ptr(None), 0, _st()), "rr_fundamental_dlt")
+    return F
+
+
+EPI_KINDS = {"sampson": E.RR_EPI_SAMPSON, "symmetrical": E.RR_EPI_SYMMETRICAL}
+
+
+def epipolar_distance(pts1, pts2, F, off, kind, squared=True, eps=1e-8):
+    """rr_epipolar_distance: pts1, pts2 float64 [rows, 2], F float64 [P, 3, 3], device int64 offsets
+    [P + 1] covering every row -> float64 [rows].  No synchronisation."""
+    E.require_gpu(pts1, pts2, F, off)
+    if pts1.dim() != 2 or pts1.shape[1] != 2 or pts1.shape != pts2.shape:
+        raise RuntimeError("epipolar distance: points must be [rows, 2] on both sides, got %s and %s"
+                           % (tuple(pts1.shape), tuple(pts2.shape)))
+    if any(t.dtype != torch.float64 or not t.is_contiguous() for t in (pts1, pts2, F)):
+        raise RuntimeError("epipolar distance: points and F must be contiguous float64")
+    if off.dtype != torch.int64 or off.numel() < 1 or tuple(F.shape) != (off.numel() - 1, 3, 3):
+        raise RuntimeError("epipolar distance: offsets int64 [P + 1] and F [P, 3, 3]")
+    rows, npairs = pts1.shape[0], off.numel() - 1
+    out = torch.empty(rows, dtype=torch.float64, device=pts1.device)
+    E.check(E.lib().rr_epipolar_distance(E.ptr(pts1), E.ptr(pts2), E.ptr(F), E.ptr(off), rows, npairs, EPI_KINDS[kind],
+                                         1 if squared else 0, float(eps), E.ptr(out), _st()), "rr_epipolar_distance")
+    return out
 
 
 # ---------------------------------------------------------------- keypoint detection

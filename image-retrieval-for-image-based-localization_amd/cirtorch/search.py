@@ -571,7 +571,8 @@ def match_pairs(desc1, desc2, mode="mnn", th=0.8, offsets1=None, offsets2=None, 
     return match.view(lead), dist.view(lead)
 
 
-def verify_pairs(kpts1, kpts2, match, th=3.0, iters=1024, refine=2, seed=0, offsets1=None, offsets2=None, max_n1=None):
+def verify_pairs(kpts1, kpts2, match, th=3.0, iters=1024, refine=2, seed=0, offsets1=None, offsets2=None, max_n1=None,
+                 model="homography"):
     """Spatial verification of matched pairs in one call (rr_verify_pairs): per pair a RANSAC
     homography over the kept matches (``match[i] >= 0``), refitted `refine` times by the
     reference's DLT on its inliers -- what ``compute_H_estimation`` (HPatchesEval.py:45-69) gets
@@ -588,7 +589,16 @@ def verify_pairs(kpts1, kpts2, match, th=3.0, iters=1024, refine=2, seed=0, offs
     `match` is exactly what ``match_pairs`` returns.  inliers counts the matches within `th`
     pixels of H, mask marks their side-1 rows; a pair with fewer than 4 matches or only degenerate
     samples gives 0, an all-zero H and an empty mask.  No device->host synchronisation:
-    graph-capturable for fixed shapes."""
+    graph-capturable for fixed shapes.
+
+    model="fundamental" (rr_verify_pairs_epipolar) verifies against the epipolar geometry of two
+    views of a 3-D scene instead: a seven-point RANSAC fundamental matrix, refitted by the
+    reference's 8-point ``find_fundamental`` on its inliers, inliers = the matches whose Sampson
+    distance is at most `th` pixels.  Same forms and outputs, with F [P, 3, 3] (unit Frobenius
+    norm, ``x2^T F x1 = 0``) in place of H; fewer than 7 matches give 0.  On a planar scene or
+    under pure rotation F is not determined and the count is inflated: use the homography there."""
+    if model not in _ops.VERIFY_MODELS:
+        raise ValueError("verify_pairs: model is 'homography' or 'fundamental', got %r" % (model,))
     if (offsets1 is None) != (offsets2 is None):
         raise ValueError("verify_pairs: give both offsets1 and offsets2 (ragged) or neither (dense)")
     if kpts1.shape[-1] != 2 or kpts2.shape[-1] != 2:
@@ -602,7 +612,8 @@ def verify_pairs(kpts1, kpts2, match, th=3.0, iters=1024, refine=2, seed=0, offs
             raise ValueError("verify_pairs: the ragged form takes [rows, 2] keypoints and match [rows1]")
         _ops.E.require_gpu(kpts1, kpts2, match, offsets1, offsets2)
         inl, H, mask = _ops.verify_pairs(kpts1.float().contiguous(), offsets1.contiguous(), kpts2.float().contiguous(),
-                                         offsets2.contiguous(), match.contiguous(), th, iters, refine, seed, max_n1)
+                                         offsets2.contiguous(), match.contiguous(), th, iters, refine, seed, max_n1,
+                                         model=model)
         return inl, H, mask.view(torch.bool)
     if kpts1.dim() != kpts2.dim() or kpts1.dim() not in (2, 3) or (kpts1.dim() == 3 and kpts1.shape[0] != kpts2.shape[0]) \
             or tuple(match.shape) != tuple(kpts1.shape[:-1]):
@@ -616,7 +627,8 @@ def verify_pairs(kpts1, kpts2, match, th=3.0, iters=1024, refine=2, seed=0, offs
     steps = torch.arange(p + 1, dtype=torch.int64, device=kpts1.device)
     inl, H, mask = _ops.verify_pairs(kpts1.float().reshape(p * n1, 2).contiguous(), steps * n1,
                                      kpts2.float().reshape(p * n2, 2).contiguous(), steps * n2,
-                                     match.reshape(p * n1).contiguous(), th, iters, refine, seed, n1, covered=True)
+                                     match.reshape(p * n1).contiguous(), th, iters, refine, seed, n1, covered=True,
+                                     model=model)
     return inl, H, mask.view(torch.bool).view(match.shape)
 
 

@@ -453,6 +453,87 @@ int rr_verify_pairs(const float* kp1, const long long* off1, long long rows1, co
 int rr_homography_dlt(const double* pts1, const double* pts2, const double* weights, const long long* off,
                       long long rows, int npairs, double* H, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Epipolar verification of matched pairs (rr_epipolar.hip): a RANSAC fundamental matrix per pair,
+ * its inlier count and mask -- the model for two views of a 3-D scene from different positions,
+ * where correct matches at different depths share no homography.  Brings
+ * cirtorch/geometry/epipolar/fundamental.py:6-86 and metrics.py:4-83 to the device.  The
+ * arguments, the float64 arithmetic, the fixed summation order and the independence of npairs and
+ * the launch are those of rr_verify_pairs; F [npairs][3][3] float64 row-major satisfies
+ * [x2, y2, 1] F [x1, y1, 1]^T = 0.  Per pair p:
+ *  a. records: step a of rr_verify_pairs.
+ *  b. hypothesis t in [0, iters): seven distinct record indices by the hash and the partial
+ *     Fisher-Yates draw of rr_verify_pairs with j = 0 .. 6 (its first four are that entry's four).
+ *     The seven-point solver, on each side: u = s x + tx, v = s y + ty with (mx, my) the mean of
+ *     the seven points, s = sqrt(2) / (mean distance to it + 1e-8), tx = -s mx, ty = -s my (the
+ *     transform T of normalize_points; sqrt(2) is the float32 value, as below).  The 7 x 9 system
+ *     has the rows [u2 u1, u2 v1, u2, v2 u1, v2 v1, v2, u1, v1, 1] (fundamental.py:69).  F1 and F2
+ *     are the vectors of its null space whose last two entries are (1, 0) and (0, 1), as 3 x 3
+ *     row-major matrices; a system whose leading 7 x 7 block is singular has no such basis, its
+ *     entries are not finite and the hypothesis scores 0.  With D = F1 - F2 and
+ *     det3(a, b, c) = a0 (b1 c2 - b2 c1) - a1 (b0 c2 - b2 c0) + a2 (b0 c1 - b1 c0) on rows, the cubic
+ *     det(l F1 + (1 - l) F2) = det(F2 + l D) = c0 + c1 l + c2 l^2 + c3 l^3 has
+ *       c0 = det3(F2_0, F2_1, F2_2),  c3 = det3(D_0, D_1, D_2),
+ *       c1 = det3(D_0, F2_1, F2_2) + det3(F2_0, D_1, F2_2) + det3(F2_0, F2_1, D_2),
+ *       c2 = det3(F2_0, D_1, D_2) + det3(D_0, F2_1, D_2) + det3(D_0, D_1, F2_2).
+ *     Cubic rule: c3 == 0 (or any value not finite) gives no root -- F2 alone, the root at
+ *     infinity, is not tried.  Otherwise a = c2 / c3, b = c1 / c3, c = c0 / c3,
+ *     Q = (a^2 - 3 b) / 9, R = (2 a^3 - 9 a b + 27 c) / 54.  R^2 < Q^3: three real roots
+ *       l_k = -2 sqrt(Q) cos((theta + 2 pi k) / 3) - a / 3,  theta = acos(clamp(R / sqrt(Q^3), -1, 1)),
+ *     in ascending order k = 0, -1, +1.  R^2 >= Q^3 (a double root included): the one root
+ *       l = A + B - a / 3,  A = -sign(R) cbrt(|R| + sqrt(R^2 - Q^3)),  B = Q / A (0 when A == 0).
+ *     Root number r (0, 1, 2 in ascending l) gives F = T2^T (F2 + l D) T1; a root whose F has an
+ *     entry that is not finite scores 0.
+ *  c. score of a root: the number of records with den > 0 and num <= th^2 den, where
+ *     num = ([x2, y2, 1] F [x1, y1, 1]^T)^2 and den = (F x1)_0^2 + (F x1)_1^2 + (F^T x2)_0^2 +
+ *     (F^T x2)_1^2 -- the squared Sampson distance of metrics.py:33-38 at most th^2 (th in pixels),
+ *     without the division.  The winner is (score desc, t asc, root asc).
+ *  d. refit, `refine` times: S = the inliers of F; when |S| >= 8, F' = the unweighted
+ *     rr_fundamental_dlt fit on S; F' replaces F when it is finite and score(F') >= score(F),
+ *     otherwise (and when |S| < 8) the refit stops.
+ *  e. inliers[p] = score(F); mask [rows1] uint8 = 1 on the side-1 rows that are inliers of F
+ *     (every row of the pair is written); then F is scaled to unit Frobenius norm with its entry
+ *     of largest magnitude positive (the lowest row-major index among equal magnitudes).  It is
+ *     not divided by F[2][2]: a sideways translation has F[2][2] = 0.  M < 7 or no root with a
+ *     score above 0: inliers 0, F all zeros, mask 0.
+ * On a planar scene, or between views that differ by a pure rotation, F is not determined: the
+ * count is inflated and rr_verify_pairs is the model to use.  There is no degeneracy test.
+ * workspace: rr_verify_epipolar_workspace_bytes(rows1, npairs, iters).  Nothing waits for the host
+ * (graph-capturable).  Bad arguments are refused as by rr_verify_pairs, before anything is
+ * enqueued; npairs == 0 returns RR_OK and launches nothing. */
+size_t rr_verify_epipolar_workspace_bytes(long long rows1, int npairs, int iters);
+int rr_verify_pairs_epipolar(const float* kp1, const long long* off1, long long rows1, const float* kp2,
+                             const long long* off2, long long rows2, const long long* match, int npairs, int max_n1,
+                             double th, int iters, int refine, unsigned long long seed, int* inliers, double* F,
+                             unsigned char* mask, void* workspace, size_t workspace_bytes, void* stream);
+/* Batched weighted 8-point fit: find_fundamental of cirtorch/geometry/epipolar/fundamental.py:49-86
+ * for npairs ragged point sets in one launch; the device routine of step d above.  Arguments as
+ * rr_homography_dlt (pts 16-byte aligned float64, weights or NULL, DEVICE offsets).
+ *   F [npairs][3][3]  float64; all zeros for a set of fewer than 8 points
+ * normalize_points on all points of the set, each side (weights do not enter it; sqrt(2) is the
+ * float32 value the reference's torch.sqrt(torch.tensor(2.)) yields); X^T W X of the rows
+ * [u2 u1, u2 v1, u2, v2 u1, v2 v1, v2, u1, v1, 1], summed as sum w (p2 p2^T) (x) (p1 p1^T), p = (u, v, 1);
+ * the eigenvector of its smallest eigenvalue by the cyclic Jacobi of rr_homography_dlt, as a
+ * 3 x 3 matrix f; the rank-2 projection f - (f v3) v3^T, v3 the eigenvector of the smallest
+ * eigenvalue of f^T f (cyclic Jacobi on the 3 x 3, pairs (0, 1), (0, 2), (1, 2), the same skip
+ * criterion) -- equal to the reference's U diag(s1, s2, 0) V^T; then F = T2^T f T1 and
+ * normalize_transformation: F / (F[2][2] + 1e-8) where |F[2][2]| > 1e-8, F itself otherwise.
+ * workspace: none is needed (NULL, 0); the arguments are reserved. */
+int rr_fundamental_dlt(const double* pts1, const double* pts2, const double* weights, const long long* off,
+                       long long rows, int npairs, double* F, void* workspace, size_t workspace_bytes, void* stream);
+/* Epipolar distances of correspondences under a fundamental matrix per set:
+ * sampson_epipolar_distance and symmetrical_epipolar_distance of metrics.py:4-83.
+ *   pts1, pts2 [rows][2]  float64 (x, y), 16-byte aligned; set p is rows off[p] .. off[p + 1]
+ *   F [npairs][3][3]      float64;  off DEVICE int64 [npairs + 1]
+ *   out [rows]            float64; rows of no set are not written
+ * With num, d1 = (F x1)_0^2 + (F x1)_1^2 and d2 = (F^T x2)_0^2 + (F^T x2)_1^2 of step c above:
+ * RR_EPI_SAMPSON num / (d1 + d2), RR_EPI_SYMMETRICAL num (1 / d1 + 1 / d2); squared = 0 returns
+ * sqrt(that + eps).  A zero denominator yields what IEEE division yields, as in the reference.
+ * Bad arguments (null pointers, an unknown kind, squared not 0 / 1, eps negative or not finite)
+ * return an error before anything is enqueued; npairs == 0 returns RR_OK. */
+enum rr_epi_kind { RR_EPI_SAMPSON = 0, RR_EPI_SYMMETRICAL = 1 };
+int rr_epipolar_distance(const double* pts1, const double* pts2, const double* F, const long long* off, long long rows,
+                         int npairs, int kind, int squared, double eps, double* out, void* stream);
+
 /* Keypoint detection (rr_detect.hip): corner / blob responses, 2-D non-maxima suppression and the
  * best N local maxima per image.  Replaces harris_response, gftt_response and hessian_response of
  * cirtorch/features/responses.py:8-103 (spatial_gradient of cirtorch/filters/sobel.py:12-45,
