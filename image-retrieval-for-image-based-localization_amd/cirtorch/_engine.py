@@ -106,6 +106,10 @@ _SIGS = {
                                   _vp, _sz, _vp], _i),
     "rr_fundamental_dlt": ([_vp, _vp, _vp, _vp, _ll, _i, _vp, _vp, _sz, _vp], _i),
     "rr_epipolar_distance": ([_vp, _vp, _vp, _vp, _ll, _i, _i, _i, _d, _vp, _vp], _i),
+    "rr_recover_pose": ([_vp, _vp, _ll, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                         _vp], _i),
+    "rr_triangulate_points": ([_vp, _vp, _vp, _vp, _vp, _ll, _i, _vp, _vp], _i),
+    "rr_essential_decompose": ([_vp, _i, _vp, _vp, _vp, _vp], _i),
     "rr_detect_workspace_bytes": ([_i, _i, _i, _i], _sz),
     "rr_response": ([_vp, _i, _i, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp], _i),
     "rr_nms2d": ([_vp, _ll, _i, _i, _i, _i, _vp, _vp], _i),

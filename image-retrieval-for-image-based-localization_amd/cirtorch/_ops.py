@@ -801,6 +801,78 @@ def epipolar_distance(pts1, pts2, F, off, kind, squared=True, eps=1e-8):
     return out
 
 
+# ---------------------------------------------------------------- relative pose
+def _mat33(m, npairs, what):
+    if m.dtype != torch.float64 or tuple(m.shape) != (npairs, 3, 3) or not m.is_contiguous():
+        raise RuntimeError("pose: %s must be contiguous float64 [P, 3, 3], got %s %s" % (what, m.dtype, tuple(m.shape)))
+
+
+def recover_pose(kp1, off1, kp2, off2, match, mask, F, K1, K2, max_n1=None, covered=False):
+    """rr_recover_pose: the keypoints, offsets and match of verify_pairs, mask uint8 / bool [rows1] or
+    None, F, K1, K2 float64 [P, 3, 3] -> (R [P, 3, 3], t [P, 3], E [P, 3, 3] float64, front int32 [P],
+    points3d float64 [rows1, 3], front_mask uint8 [rows1]).  covered=True: the pairs cover every
+    side-1 row (the per-row outputs are not pre-filled with 0).  No synchronisation."""
+    E.require_gpu(kp1, off1, kp2, off2, match, mask, F, K1, K2)
+    if kp1.dim() != 2 or kp2.dim() != 2 or kp1.shape[1] != 2 or kp2.shape[1] != 2:
+        raise RuntimeError("pose: keypoints must be [rows, 2], got %s and %s" % (tuple(kp1.shape), tuple(kp2.shape)))
+    if kp1.dtype != torch.float32 or kp2.dtype != torch.float32 or not kp1.is_contiguous() or not kp2.is_contiguous():
+        raise RuntimeError("pose: keypoints must be contiguous float32 rows")
+    if off1.dtype != torch.int64 or off2.dtype != torch.int64 or off1.numel() != off2.numel() or off1.numel() < 1:
+        raise RuntimeError("pose: offsets must be int64 [P + 1] for both sides")
+    rows1, rows2, npairs = kp1.shape[0], kp2.shape[0], off1.numel() - 1
+    if match.dtype != torch.int64 or match.dim() != 1 or match.shape[0] != rows1 or not match.is_contiguous():
+        raise RuntimeError("pose: match must be contiguous int64 [rows1]")
+    if mask is not None:
+        if mask.dtype not in (torch.uint8, torch.bool) or tuple(mask.shape) != (rows1,) or not mask.is_contiguous():
+            raise RuntimeError("pose: mask must be contiguous uint8 or bool [rows1]")
+    for m, what in ((F, "F"), (K1, "K1"), (K2, "K2")):
+        _mat33(m, npairs, what)
+    max_n1 = rows1 if max_n1 is None else min(int(max_n1), rows1)
+    dev = kp1.device
+    new = torch.empty if covered and npairs else torch.zeros
+    R = torch.empty((npairs, 3, 3), dtype=torch.float64, device=dev)   # written for every pair
+    t = torch.empty((npairs, 3), dtype=torch.float64, device=dev)
+    Em = torch.empty((npairs, 3, 3), dtype=torch.float64, device=dev)
+    front = torch.empty(npairs, dtype=torch.int32, device=dev)
+    pts = new((rows1, 3), dtype=torch.float64, device=dev)
+    fmask = new(rows1, dtype=torch.uint8, device=dev)
+    E.check(E.lib().rr_recover_pose(E.ptr(kp1), E.ptr(off1), rows1, E.ptr(kp2), E.ptr(off2), rows2, E.ptr(match),
+                                    E.ptr(mask), E.ptr(F), E.ptr(K1), E.ptr(K2), npairs, max_n1, E.ptr(R), E.ptr(t),
+                                    E.ptr(Em), E.ptr(front), E.ptr(pts), E.ptr(fmask), E.ptr(None), 0, _st()),
+            "rr_recover_pose")
+    return R, t, Em, front, pts, fmask
+
+
+def triangulate_points(pts1, pts2, P1, P2, off):
+    """rr_triangulate_points: pts1, pts2 float64 [rows, 2], P1, P2 float64 [P, 3, 4], device int64
+    offsets [P + 1] covering every row -> X float64 [rows, 3].  No synchronisation."""
+    E.require_gpu(pts1, pts2, P1, P2, off)
+    if pts1.dim() != 2 or pts1.shape[1] != 2 or pts1.shape != pts2.shape:
+        raise RuntimeError("triangulate: points must be [rows, 2] on both sides, got %s and %s"
+                           % (tuple(pts1.shape), tuple(pts2.shape)))
+    if any(x.dtype != torch.float64 or not x.is_contiguous() for x in (pts1, pts2, P1, P2)):
+        raise RuntimeError("triangulate: points and projections must be contiguous float64")
+    if off.dtype != torch.int64 or off.numel() < 1 or tuple(P1.shape) != (off.numel() - 1, 3, 4) or P2.shape != P1.shape:
+        raise RuntimeError("triangulate: offsets int64 [P + 1] and projections [P, 3, 4]")
+    rows, npairs = pts1.shape[0], off.numel() - 1
+    X = torch.empty((rows, 3), dtype=torch.float64, device=pts1.device)
+    E.check(E.lib().rr_triangulate_points(E.ptr(pts1), E.ptr(pts2), E.ptr(P1), E.ptr(P2), E.ptr(off), rows, npairs,
+                                          E.ptr(X), _st()), "rr_triangulate_points")
+    return X
+
+
+def essential_decompose(Em):
+    """rr_essential_decompose: E float64 [n, 3, 3] -> (R1, R2 [n, 3, 3], t [n, 3]) float64.  No synchronisation."""
+    E.require_gpu(Em)
+    if Em.dtype != torch.float64 or Em.dim() != 3 or tuple(Em.shape[1:]) != (3, 3) or not Em.is_contiguous():
+        raise RuntimeError("essential: E must be contiguous float64 [n, 3, 3], got %s %s" % (Em.dtype, tuple(Em.shape)))
+    n = Em.shape[0]
+    R1, R2 = torch.empty_like(Em), torch.empty_like(Em)
+    t = torch.empty((n, 3), dtype=torch.float64, device=Em.device)
+    E.check(E.lib().rr_essential_decompose(E.ptr(Em), n, E.ptr(R1), E.ptr(R2), E.ptr(t), _st()), "rr_essential_decompose")
+    return R1, R2, t
+
+
 # ---------------------------------------------------------------- keypoint detection
 RESPONSES = {"harris": E.RR_RESP_HARRIS, "gftt": E.RR_RESP_GFTT, "hessian": E.RR_RESP_HESSIAN}
 NMS_SIZES = (3, 5, 7, 9)

@@ -632,6 +632,82 @@ def verify_pairs(kpts1, kpts2, match, th=3.0, iters=1024, refine=2, seed=0, offs
     return inl, H, mask.view(torch.bool).view(match.shape)
 
 
+def _pose_mats(m, p, what):
+    """[3, 3] (one for every pair) or [P, 3, 3] -> contiguous float64 [P, 3, 3]"""
+    if tuple(m.shape) == (3, 3):
+        m = m.unsqueeze(0).expand(p, 3, 3)
+    if tuple(m.shape) != (p, 3, 3):
+        raise ValueError("recover_pose: %s must be [3, 3] or [P, 3, 3] with P = %d, got %s" % (what, p, tuple(m.shape)))
+    return m.double().contiguous()
+
+
+def recover_pose(kpts1, kpts2, match, F, K1, K2, mask=None, offsets1=None, offsets2=None, max_n1=None):
+    """The camera motion between the two views of each verified pair, and the 3-D points its matches
+    triangulate to, in one call (rr_recover_pose) -- the step after
+    ``verify_pairs(model="fundamental")``, every output of which is an input here:
+
+        inl, F, mask = verify_pairs(q_kpts, db_kpts, match, th=1.5, model="fundamental")
+        R, t, X, front_mask, front = recover_pose(q_kpts, db_kpts, match, F, Kq, Kdb, mask=mask)
+
+    Per pair: E = K2^T F K1 (``essential_from_fundamental``), its four candidate motions
+    (``decompose_essential_matrix``), the matches triangulated under each (``triangulate_points``) and
+    the candidate with the most points in front of both cameras
+    (``motion_from_essential_choose_solution``), all in float64 on the device without a
+    ``torch.svd``.  Each pair chooses its own solution (the reference applies the choice of pair 0 to
+    a whole batch).
+
+    dense   kpts1 [P, N1, 2], kpts2 [P, N2, 2], match int64 [P, N1], mask bool [P, N1] or None
+            (or [N1, 2], [N2, 2], [N1]), F [P, 3, 3] (or [3, 3] for one pair), K1 / K2 [3, 3] (one
+            camera for every pair) or [P, 3, 3]
+            -> R float64 [P, 3, 3], t float64 [P, 3, 1] (unit norm: the scale is not observable),
+               points3d float64 [P, N1, 3] in the first camera's frame (zeros on unused rows),
+               front_mask bool [P, N1], front int32 [P] (the number of points in front)
+    ragged  kpts1 [rows1, 2], kpts2 [rows2, 2], match [rows1], mask [rows1] with the device int64
+            offsets1 / offsets2 [P + 1] of ``verify_pairs`` -> points3d [rows1, 3], front_mask [rows1]
+
+    mask=None uses every kept match.  A pair whose F is all zero (a failed verification), or with no
+    match to use, gives zeros and front 0.  ``x2 = K2 (R X + t)``, ``x1 = K1 X``.  No device->host
+    synchronisation: graph-capturable for fixed shapes."""
+    if (offsets1 is None) != (offsets2 is None):
+        raise ValueError("recover_pose: give both offsets1 and offsets2 (ragged) or neither (dense)")
+    if kpts1.shape[-1] != 2 or kpts2.shape[-1] != 2:
+        raise ValueError("recover_pose: keypoints are (x, y) rows, got %s and %s" % (tuple(kpts1.shape), tuple(kpts2.shape)))
+    if match.dtype != torch.int64:
+        raise ValueError("recover_pose: match must be int64 (the output of match_pairs), got %s" % match.dtype)
+    if mask is not None and (tuple(mask.shape) != tuple(match.shape) or mask.dtype not in (torch.bool, torch.uint8)):
+        raise ValueError("recover_pose: mask must be bool or uint8 of match's shape %s, got %s %s"
+                         % (tuple(match.shape), mask.dtype, tuple(mask.shape)))
+    if offsets1 is not None:
+        if kpts1.dim() != 2 or kpts2.dim() != 2 or match.dim() != 1 or match.shape[0] != kpts1.shape[0]:
+            raise ValueError("recover_pose: the ragged form takes [rows, 2] keypoints and match [rows1]")
+        p = offsets1.numel() - 1
+        if offsets2.numel() != p + 1 or p < 0:
+            raise ValueError("recover_pose: offsets1 and offsets2 must both be [P + 1]")
+        Fm, Ka, Kb = _pose_mats(F, p, "F"), _pose_mats(K1, p, "K1"), _pose_mats(K2, p, "K2")
+        _ops.E.require_gpu(kpts1, kpts2, match, mask, offsets1, offsets2, F, K1, K2)
+        R, t, _, front, pts, fmask = _ops.recover_pose(kpts1.float().contiguous(), offsets1.contiguous(),
+                                                       kpts2.float().contiguous(), offsets2.contiguous(), match.contiguous(),
+                                                       None if mask is None else mask.contiguous(), Fm, Ka, Kb, max_n1)
+        return R, t.unsqueeze(-1), pts, fmask.view(torch.bool), front
+    if kpts1.dim() != kpts2.dim() or kpts1.dim() not in (2, 3) or (kpts1.dim() == 3 and kpts1.shape[0] != kpts2.shape[0]) \
+            or tuple(match.shape) != tuple(kpts1.shape[:-1]):
+        raise ValueError("recover_pose: dense keypoints are [P, N, 2] or [N, 2] on both sides with match [P, N1] or [N1], "
+                         "got %s, %s and %s" % (tuple(kpts1.shape), tuple(kpts2.shape), tuple(match.shape)))
+    p = kpts1.shape[0] if kpts1.dim() == 3 else 1
+    n1, n2 = kpts1.shape[-2], kpts2.shape[-2]
+    if max_n1 is not None and int(max_n1) < n1:
+        raise ValueError("recover_pose: max_n1 = %d below the pairs' length %d" % (int(max_n1), n1))
+    Fm, Ka, Kb = _pose_mats(F, p, "F"), _pose_mats(K1, p, "K1"), _pose_mats(K2, p, "K2")
+    _ops.E.require_gpu(kpts1, kpts2, match, mask, F, K1, K2)
+    steps = torch.arange(p + 1, dtype=torch.int64, device=kpts1.device)
+    R, t, _, front, pts, fmask = _ops.recover_pose(kpts1.float().reshape(p * n1, 2).contiguous(), steps * n1,
+                                                   kpts2.float().reshape(p * n2, 2).contiguous(), steps * n2,
+                                                   match.reshape(p * n1).contiguous(),
+                                                   None if mask is None else mask.reshape(p * n1).contiguous(), Fm, Ka, Kb,
+                                                   n1, covered=True)
+    return R, t.unsqueeze(-1), pts.view(tuple(match.shape) + (3,)), fmask.view(torch.bool).view(match.shape), front
+
+
 def rerank_by_inliers(idx, inliers):
     """Re-order a [k, Q] shortlist (``knn``'s ranks: column q lists query q's database rows, best
     first) by the verified inlier counts [k, Q] of its entries: (inliers desc, original rank

@@ -300,31 +300,6 @@ struct SrcInliersF {     // the inliers of f among the records of a pair, weight
     }
 };
 
-// one Jacobi rotation of the symmetric 3 x 3 matrix g in registers (the criterion and the angle of
-// jacobi_round), eigenvectors accumulated in the columns of v
-template <int P, int Q>
-__device__ __forceinline__ bool rot3(double (&g)[9], double (&v)[9]) {
-    constexpr int R = 3 - P - Q;
-    const double apq = g[3 * P + Q], app = g[4 * P], aqq = g[4 * Q];
-    if (!(fabs(apq) > V_JTOL * sqrt(fabs(app * aqq)))) return false;
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(fma(theta, theta, 1.0)));
-    const double c = 1.0 / sqrt(fma(t, t, 1.0)), s = t * c;
-    const double arp = g[3 * R + P], arq = g[3 * R + Q];
-    g[4 * P] = app - t * apq;
-    g[4 * Q] = aqq + t * apq;
-    g[3 * P + Q] = g[3 * Q + P] = 0.0;
-    g[3 * R + P] = g[3 * P + R] = c * arp - s * arq;
-    g[3 * R + Q] = g[3 * Q + R] = s * arp + c * arq;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double x = v[3 * k + P], y = v[3 * k + Q];
-        v[3 * k + P] = c * x - s * y;
-        v[3 * k + Q] = s * x + c * y;
-    }
-    return true;
-}
-
 // f <- f - (f v3) v3^T, v3 the eigenvector of the smallest eigenvalue of f^T f (ties: the lower
 // index): the reference's U diag(s1, s2, 0) V^T without a full SVD
 __device__ __forceinline__ void rank2(double (&f)[9]) {

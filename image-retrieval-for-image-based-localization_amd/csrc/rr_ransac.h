@@ -1,8 +1,9 @@
 // librr.so — what the two geometric verifiers (rr_verify.hip: homography, rr_epipolar.hip:
-// fundamental matrix) share: the pair ranges, the counter-hash sampler of rr.h, the compaction of
-// kept matches into records, the block reductions with one fixed order, the round-robin cyclic
-// Jacobi on a symmetric 9 x 9 matrix in LDS and the workspace layout.  Both files compile this
-// with the same floating-point settings, so a shared routine yields the same bits in either.
+// fundamental matrix) and the pose entry after them (rr_pose.hip) share: the pair ranges, the
+// counter-hash sampler of rr.h, the compaction of kept matches into records, the block reductions
+// with one fixed order, the round-robin cyclic Jacobi on a symmetric 9 x 9 matrix in LDS, the
+// cyclic Jacobi on a symmetric 3 x 3 in registers and the workspace layout.  The files compile
+// this with the same floating-point settings, so a shared routine yields the same bits in each.
 #pragma once
 #include "rr_internal.h"
 #include "rr_workspace.h"
@@ -213,9 +214,36 @@ __device__ __forceinline__ void jacobi_smallest9(double* A, double* V, double (&
     for (int i = 0; i < 9; ++i) e9[i] = V[9 * i + m];
 }
 
+// ---------------------------------------------------------------- cyclic Jacobi, 3 x 3 in registers
+// one Jacobi rotation of the symmetric 3 x 3 matrix g in registers (the criterion and the angle of
+// jacobi_round), eigenvectors accumulated in the columns of v
+template <int P, int Q>
+__device__ __forceinline__ bool rot3(double (&g)[9], double (&v)[9]) {
+    constexpr int R = 3 - P - Q;
+    const double apq = g[3 * P + Q], app = g[4 * P], aqq = g[4 * Q];
+    if (!(fabs(apq) > V_JTOL * sqrt(fabs(app * aqq)))) return false;
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(fma(theta, theta, 1.0)));
+    const double c = 1.0 / sqrt(fma(t, t, 1.0)), s = t * c;
+    const double arp = g[3 * R + P], arq = g[3 * R + Q];
+    g[4 * P] = app - t * apq;
+    g[4 * Q] = aqq + t * apq;
+    g[3 * P + Q] = g[3 * Q + P] = 0.0;
+    g[3 * R + P] = g[3 * P + R] = c * arp - s * arq;
+    g[3 * R + Q] = g[3 * Q + R] = s * arp + c * arq;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double x = v[3 * k + P], y = v[3 * k + Q];
+        v[3 * k + P] = c * x - s * y;
+        v[3 * k + Q] = s * x + c * y;
+    }
+    return true;
+}
+
 // ---------------------------------------------------------------- records
 // one block per pair: the kept matches (0 <= match[i] < n2) in ascending side-1 index become
 // records (x1, y1, x2, y2) of four doubles at the pair's side-1 offset; cnt[p] = M_p
+[[maybe_unused]]   // rr_pose.hip includes this header and reads the rows itself
 __global__ void __launch_bounds__(V_TB) k_verify_compact(const float* __restrict__ kp1, const long long* __restrict__ off1,
                                                          long long rows1, const float* __restrict__ kp2,
                                                          const long long* __restrict__ off2, long long rows2,

@@ -534,6 +534,83 @@ enum rr_epi_kind { RR_EPI_SAMPSON = 0, RR_EPI_SYMMETRICAL = 1 };
 int rr_epipolar_distance(const double* pts1, const double* pts2, const double* F, const long long* off, long long rows,
                          int npairs, int kind, int squared, double eps, double* out, void* stream);
 
+/* Relative pose of verified pairs (rr_pose.hip): the essential matrix of a fundamental matrix, its
+ * four candidate motions, the triangulation of the pair's matches under each and the choice of the
+ * motion that puts the most points in front of both cameras.  Brings essential_from_fundamental
+ * (cirtorch/geometry/epipolar/essential.py:8-18), decompose_essential_matrix (:21-54),
+ * motion_from_essential (:75-89), motion_from_essential_choose_solution (:92-153), triangulate_points
+ * (triangulation.py:7-41), projection_from_KRt and depth (projection.py:60-78, :111-119) and
+ * convert_points_from_homogeneous (conversions.py:67-83) to the device.  kp1, off1, rows1, kp2, off2,
+ * rows2, match, npairs and max_n1 are those of rr_verify_pairs_epipolar, and every output of that
+ * entry is an input here.
+ *   mask [rows1]                 uint8 as rr_verify_pairs_epipolar writes it, or NULL: every matched row
+ *   F, K1, K2 [npairs][3][3]     float64 row-major: the fundamental matrix ([x2, y2, 1] F [x1, y1, 1]^T = 0)
+ *                                and the intrinsics of the two views
+ *   R, E [npairs][3][3]          float64;  t [npairs][3] float64, unit norm;  front [npairs] int32
+ *   points3d [rows1][3]          float64, in the frame of the first camera, in units of |t|
+ *   front_mask [rows1]           uint8
+ * All arithmetic is float64 and a result depends on the pair's own data only.  Per pair p:
+ *  a. used records: the kept rows of step a of rr_verify_pairs (0 <= match[i] < n2, i < max_n1) with,
+ *     when mask is given, mask[i] != 0; as (x1, y1, x2, y2) in float64.
+ *  b. E0 = K2^T F K1 (essential.py:18).  Its singular value decomposition: the eigenvectors of
+ *     E0^T E0 by the 3 x 3 cyclic Jacobi of rr_fundamental_dlt, v0 and v1 those of the largest and
+ *     the second largest eigenvalue (the lower index first among equals); a_i = E0 v_i,
+ *     u0 = a0 / |a0|, u1 = b / |b| with b = a1 - (u0 . a1) u0, u2 = u0 x u1, v2 = v0 x v1.  U = [u0 u1 u2]
+ *     and V = [v0 v1 v2] have determinant +1, which is the sign fix of essential.py:33-40 in closed
+ *     form.  E = u0 v0^T + u1 v1^T = U diag(1, 1, 0) V^T.
+ *  c. candidates 0 .. 3: (Ra, t), (Ra, -t), (Rb, t), (Rb, -t) with W = [[0, -1, 0], [1, 0, 0], [0, 0, 1]],
+ *     Ra = U W V^T = u1 v0^T - u0 v1^T + u2 v2^T, Rb = U W^T V^T = u0 v1^T - u1 v0^T + u2 v2^T, t = u2.
+ *     The labelling of Ra / Rb and the sign of t follow the signs of v0 and v1, which the Jacobi
+ *     iteration fixes and another SVD would fix otherwise: the candidate order is this entry's own,
+ *     not the reference's.  The set of four is the same, and so is the winner whenever it is unique.
+ *  d. every used record is triangulated under each candidate as triangulate_points does, in pixel
+ *     units: P1 = K1 [I | 0], P2 = K2 [R | t]; the 4 x 4 system with rows x1 P1_2 - P1_0,
+ *     y1 P1_2 - P1_1, x2 P2_2 - P2_0, y2 P2_2 - P2_1 (P_r: row r; triangulation.py:27-31); its right
+ *     singular vector h of the smallest singular value (the lower index among equals) by one-sided
+ *     (Hestenes) Jacobi on the columns of the 4 x 4 itself -- not on A^T A, whose condition number is
+ *     the square --: column pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), a pair is rotated where
+ *     |c_p . c_q| > 2^-52 sqrt(|c_p|^2 |c_q|^2) (the criterion and the angle of rr_homography_dlt with
+ *     a_pp = |c_p|^2, a_qq = |c_q|^2, a_pq = c_p . c_q), the same rotation applied to the identity
+ *     gives the singular vectors, until a sweep rotates nothing or RR_POSE_SWEEPS sweeps are done.
+ *     X = s (h0, h1, h2), s = 1 / h3 where |h3| > 1e-8 and 1 otherwise (conversions.py:77-83).  The
+ *     depths are X_z and (R X)_z + t_z; a record is in front under a candidate when both are > 0.
+ *  e. the winner is the candidate with the most records in front, the lowest index among equals.
+ *     R, t, front[p] (its count), front_mask (1 on its records in front) and points3d (its X on used
+ *     rows, zeros on the other rows) come from the winner; every row of the pair (below max_n1) is
+ *     written.  An F with an entry that is not finite or with all entries zero (what
+ *     rr_verify_pairs_epipolar returns for a failed pair), a K with an entry that is not finite,
+ *     |a0| not finite, |a1| or |b| not > 0, and a pair with no used record give zeros in R, t, E,
+ *     points3d and front_mask and front = 0.
+ * Deliberate deviation: motion_from_essential_choose_solution indexes Rs[:, mask_indices][:, 0, 0]
+ * (essential.py:149-151), which for a batch of more than one applies the choice of pair 0 to every
+ * pair.  Here every pair chooses its own solution.
+ * The fused entry shares its device routines with the two entries below: its result has the bits of
+ * rr_essential_decompose on E0, rr_triangulate_points under P1 and each candidate's P2 and a count
+ * of the depths (E0 and the P are products inside this entry; with K1 = K2 = I they are exact and
+ * the chain can be formed outside).  workspace: none is needed (NULL, 0); the arguments
+ * are reserved.  Nothing waits for the host (graph-capturable).  Bad arguments (null pointers, negative
+ * sizes, max_n1 > rows1, misaligned keypoints) return an error before anything is enqueued;
+ * npairs == 0 returns RR_OK and launches nothing. */
+#define RR_POSE_SWEEPS 30
+int rr_recover_pose(const float* kp1, const long long* off1, long long rows1, const float* kp2, const long long* off2,
+                    long long rows2, const long long* match, const unsigned char* mask, const double* F, const double* K1,
+                    const double* K2, int npairs, int max_n1, double* R, double* t, double* E, int* front,
+                    double* points3d, unsigned char* front_mask, void* workspace, size_t workspace_bytes, void* stream);
+/* Batched triangulation: triangulate_points of triangulation.py:7-41 for npairs ragged point sets
+ * in one launch; the device routine of step d above.
+ *   pts1, pts2 [rows][2]   float64 (x, y), 16-byte aligned; set p is rows off[p] .. off[p + 1]
+ *   P1, P2 [npairs][3][4]  float64 row-major projection matrices of the two views
+ *   off                    DEVICE int64 [npairs + 1]
+ *   X [rows][3]            float64; rows of no set are not written
+ * Bad arguments are refused before anything is enqueued; npairs == 0 returns RR_OK. */
+int rr_triangulate_points(const double* pts1, const double* pts2, const double* P1, const double* P2, const long long* off,
+                          long long rows, int npairs, double* X, void* stream);
+/* Steps b and c above for n essential matrices: decompose_essential_matrix of essential.py:21-54.
+ *   E [n][3][3] float64 -> R1 = Ra, R2 = Rb [n][3][3], t [n][3] float64 (unit norm)
+ * A matrix that step e above refuses gives zeros.  n < 0 and null pointers are refused before
+ * anything is enqueued; n == 0 returns RR_OK. */
+int rr_essential_decompose(const double* E, int n, double* R1, double* R2, double* t, void* stream);
+
 /* Keypoint detection (rr_detect.hip): corner / blob responses, 2-D non-maxima suppression and the
  * best N local maxima per image.  Replaces harris_response, gftt_response and hessian_response of
  * cirtorch/features/responses.py:8-103 (spatial_gradient of cirtorch/filters/sobel.py:12-45,
