@@ -31,6 +31,10 @@ TUNE_KEYS = ("GEMM_CONFIG", "GEMM_STAGES", "GEMM_WIDE", "GEMM_ASTAT", "GEMM_XCD_
              "GRID_CUS", "GEMM8", "KNN_FUSED", "CONV3_PIPE", "STEM", "STREAM_XCD", "CONV3S", "WRES", "PAIR_MID",
              "WRES_RING")
 globals().update(("RR_TUNE_" + name, key) for key, name in enumerate(TUNE_KEYS))
+# enum rr_tune_size_key: the keys that set a length, RR_TUNE_<name> = number
+TUNE_SIZE_KEYS = {"PATCHNET_CHUNK": 32}
+globals().update(("RR_TUNE_" + name, key) for name, key in TUNE_SIZE_KEYS.items())
+RR_PATCHNET_HARDNET, RR_PATCHNET_SOSNET = 0, 1
 
 _DTYPE_CODE = {torch.float32: RR_F32, torch.bfloat16: RR_BF16, torch.float16: RR_F16,
                torch.int8: RR_I8}  # RR_I8: kNN screening only
@@ -110,6 +114,12 @@ _SIGS = {
                          _vp], _i),
     "rr_triangulate_points": ([_vp, _vp, _vp, _vp, _vp, _ll, _i, _vp, _vp], _i),
     "rr_essential_decompose": ([_vp, _i, _vp, _vp, _vp, _vp], _i),
+    "rr_patchnet_packed_bytes": ([], _sz),
+    "rr_patchnet_pack": ([ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _sz, _vp], _i),
+    "rr_patchnet_workspace_bytes": ([_ll], _sz),
+    "rr_patchnet_trunk": ([_vp, _ll, _i, _vp, _vp, _vp], _i),
+    "rr_patchnet_head": ([_vp, _ll, _i, _vp, _vp, _vp], _i),
+    "rr_patchnet_describe": ([_vp, _ll, _i, _vp, _vp, _vp, _sz, _vp], _i),
     "rr_detect_workspace_bytes": ([_i, _i, _i, _i], _sz),
     "rr_response": ([_vp, _i, _i, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp], _i),
     "rr_nms2d": ([_vp, _ll, _i, _i, _i, _i, _vp, _vp], _i),
@@ -188,10 +198,12 @@ def _tune_key(name):
     name = name[len("RR_TUNE_"):] if name.startswith("RR_TUNE_") else name
     if name in TUNE_KEYS:
         return TUNE_KEYS.index(name)
+    if name in TUNE_SIZE_KEYS:
+        return TUNE_SIZE_KEYS[name]
     try:
         return int(name)
     except ValueError:
-        raise ValueError("unknown tuning key %r (one of %s, or a number)" % (name, ", ".join(TUNE_KEYS)))
+        raise ValueError("unknown tuning key %r (one of %s, or a number)" % (name, ", ".join(TUNE_KEYS + tuple(TUNE_SIZE_KEYS))))
 
 
 def get_tuning(key):

@@ -1435,3 +1435,74 @@ def laf_affine_shape(x, lafs, count=None, ps=32, eps=1e-10, out=None):
     E.check(E.lib().rr_laf_affine_shape(E.ptr(x), n, c, h, w, int(x.dtype == torch.uint8), E.ptr(lafs), E.ptr(count), npts, ps,
                                         float(eps), E.ptr(out), E.ptr(ws), ws.numel(), _st()), "rr_laf_affine_shape")
     return out
+
+
+# ---------------------------------------------------------------- learned patch descriptors
+PATCHNET_VARIANTS = {"hardnet": E.RR_PATCHNET_HARDNET, "sosnet": E.RR_PATCHNET_SOSNET}
+PATCHNET_SHAPES = ((32, 1, 3), (32, 32, 3), (64, 32, 3), (64, 64, 3), (128, 64, 3), (128, 128, 3), (128, 128, 8))
+
+
+def _ptr_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def patchnet_pack(weights, means, variances):
+    """rr_patchnet_pack: the seven conv weights [cout, cin, k, k] and running_mean / running_var
+    [cout] of the trunk -> the packed device blob (uint8).  No synchronisation."""
+    if not (len(weights) == len(means) == len(variances) == 7):
+        raise ValueError("patchnet_pack: seven weights, means and variances")
+    E.require_gpu(*weights, *means, *variances)
+    keep = []
+    for group in (weights, means, variances):
+        keep.append([t.detach().float().contiguous() for t in group])
+    for (co, ci, k), w, m, v in zip(PATCHNET_SHAPES, *keep):
+        if tuple(w.shape) != (co, ci, k, k) or tuple(m.shape) != (co,) or tuple(v.shape) != (co,):
+            raise ValueError("patchnet_pack: expected weight %s with statistics [%d], got %s, %s, %s"
+                             % ((co, ci, k, k), co, tuple(w.shape), tuple(m.shape), tuple(v.shape)))
+    nbytes = int(E.lib().rr_patchnet_packed_bytes())
+    packed = torch.empty(nbytes, dtype=torch.uint8, device=keep[0][0].device)
+    E.check(E.lib().rr_patchnet_pack(_ptr_array(keep[0]), _ptr_array(keep[1]), _ptr_array(keep[2]), E.ptr(packed), nbytes, _st()),
+            "rr_patchnet_pack")
+    return packed
+
+
+def _patchnet_patches(patches, what):
+    patches = _patches(patches, what)
+    if tuple(patches.shape[-2:]) != (32, 32):
+        raise ValueError("%s: patches are 32 x 32, got %s" % (what, tuple(patches.shape)))
+    return patches, patches.numel() // 1024
+
+
+def patchnet_trunk(patches, packed, variant):
+    """rr_patchnet_trunk: float32 patches [..., 32, 32] -> the layer-6 maps fp16 [B, 8, 8, 128].  No synchronisation."""
+    patches, B = _patchnet_patches(patches, "patchnet_trunk")
+    out = torch.empty((B, 8, 8, 128), dtype=torch.float16, device=patches.device)
+    E.check(E.lib().rr_patchnet_trunk(E.ptr(patches), B, PATCHNET_VARIANTS[variant], E.ptr(packed), E.ptr(out), _st()),
+            "rr_patchnet_trunk")
+    return out
+
+
+def patchnet_head(maps, packed, variant):
+    """rr_patchnet_head: maps fp16 [B, 8, 8, 128] -> descriptors float32 [B, 128].  No synchronisation."""
+    E.require_gpu(maps)
+    if maps.dtype != torch.float16 or maps.dim() != 4 or tuple(maps.shape[1:]) != (8, 8, 128):
+        raise ValueError("patchnet_head: maps are fp16 [B, 8, 8, 128], got %s %s" % (maps.dtype, tuple(maps.shape)))
+    maps = maps.contiguous()
+    out = torch.empty((maps.shape[0], 128), dtype=torch.float32, device=maps.device)
+    E.check(E.lib().rr_patchnet_head(E.ptr(maps), maps.shape[0], PATCHNET_VARIANTS[variant], E.ptr(packed), E.ptr(out), _st()),
+            "rr_patchnet_head")
+    return out
+
+
+def patchnet_describe(patches, packed, variant, out=None):
+    """rr_patchnet_describe: float32 patches [..., 32, 32] -> descriptors float32 [B, 128] (into out, a
+    contiguous float32 [B, 128], when given).  No synchronisation."""
+    patches, B = _patchnet_patches(patches, "patchnet_describe")
+    if out is None:
+        out = torch.empty((B, 128), dtype=torch.float32, device=patches.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, 128) or not out.is_contiguous():
+        raise ValueError("patchnet_describe: out must be contiguous float32 [%d, 128]" % B)
+    ws = _workspace(E.lib().rr_patchnet_workspace_bytes(B), patches.device)
+    E.check(E.lib().rr_patchnet_describe(E.ptr(patches), B, PATCHNET_VARIANTS[variant], E.ptr(packed), E.ptr(out), E.ptr(ws),
+                                         ws.numel(), _st()), "rr_patchnet_describe")
+    return out

@@ -9,3 +9,5 @@ from .laf import (denormalize_laf, ellipse_to_laf, extract_patches_from_pyramid,
 from .orientation import LAFOrienter, PassLAF, PatchDominantGradientOrientation  # noqa: F401
 from .siftdesc import SIFTDescriptor, get_sift_bin_ksize_stride_pad, get_sift_pooling_kernel, sift_describe  # noqa: F401
 from .scale_space_detector import ScaleSpaceDetector  # noqa: F401
+from .hardnet import HardNet  # noqa: F401
+from .sosnet import SOSNet  # noqa: F401

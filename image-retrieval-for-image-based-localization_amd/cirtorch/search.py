@@ -481,8 +481,70 @@ def estimate_affine_shape(images, lafs, count=None, patch_size=32):
     return _ops.laf_affine_shape(images, lafs, count, int(patch_size))
 
 
+# patches the learned-descriptor path of describe_keypoints holds at a time (4 KiB each)
+LEARNED_PATCH_BUDGET = 16384
+
+
+def _describe_learned(images, kpts, count, scale, lafs, orientation, pyramid, descriptor):
+    """describe_keypoints with a HardNet / SOSNet module: frames -> patches -> rr_patchnet_describe, a
+    slice of the keypoints at a time.  Device work only."""
+    from .features.laf import _rotation, make_upright
+    from .geometry.conversions import rad2deg
+    images = _ops._describe_image(images, "describe_keypoints")
+    n = images.shape[0]
+    _ops.E.require_gpu(kpts, count, lafs)
+    _ops._no_grad("describe_keypoints", images, kpts, lafs)
+    if lafs is not None:
+        if lafs.dim() != 4 or lafs.shape[0] != n or tuple(lafs.shape[2:]) != (2, 3):
+            raise ValueError("describe_keypoints: lafs must be [%d, N, 2, 3], got %s" % (n, tuple(lafs.shape)))
+        lafs = lafs.float().contiguous()
+    else:
+        if kpts is None or kpts.dim() != 3 or kpts.shape[0] != n or kpts.shape[2] != 2:
+            raise ValueError("describe_keypoints: kpts must be [%d, N, 2], got %s"
+                             % (n, None if kpts is None else tuple(kpts.shape)))
+        if not (scale > 0.0 and scale != float("inf")):
+            raise ValueError("describe_keypoints: scale must be positive and finite, got %r" % (scale,))
+        kpts = kpts.float()
+        lafs = torch.zeros(kpts.shape[:2] + (2, 3), dtype=torch.float32, device=kpts.device)
+        lafs[..., 0, 0] = scale
+        lafs[..., 1, 1] = scale
+        lafs[..., 2] = kpts
+    npts = lafs.shape[1]
+    dev = images.device
+    if count is not None and (count.dim() != 1 or count.shape[0] != n or count.dtype != torch.int32):
+        raise ValueError("describe_keypoints: count must be int32 [%d], got %s %s" % (n, count.dtype, tuple(count.shape)))
+    # dead slots: at or past count, a (-1, -1) centre, a frame that is not finite.  They are sampled as
+    # the unit frame at the origin and their rows zeroed.
+    dead = (lafs[..., 2] == -1).all(-1) | ~torch.isfinite(lafs).all(-1).all(-1)
+    if count is not None:
+        dead |= torch.arange(npts, device=dev)[None, :] >= count[:, None]
+    safe = torch.zeros((2, 3), dtype=torch.float32, device=dev)
+    safe[0, 0] = 1.0
+    safe[1, 1] = 1.0
+    lafs = torch.where(dead[..., None, None], safe, lafs)
+    gray = images.shape[1] == 3
+    pyr = _ops.patch_pyramid(images, 32, gray)[1] if pyramid else None
+    extract = (lambda f: _ops.extract_patches_pyramid(images, f, 32, gray, pyr=pyr)) if pyramid else \
+        (lambda f: _ops.extract_patches(images, f, 32, gray))
+    desc = torch.empty((n, npts, 128), dtype=torch.float32, device=dev)
+    angles = torch.zeros((n, npts), dtype=torch.float32, device=dev)
+    step = max(1, LEARNED_PATCH_BUDGET // max(n, 1))
+    for j0 in range(0, npts, step):
+        frames = lafs[:, j0:j0 + step].contiguous()
+        if orientation:
+            frames = make_upright(frames).contiguous()
+            ang = _ops.patch_orientation(extract(frames)[:, :, 0], 36)
+            angles[:, j0:j0 + step] = ang
+            frames = torch.cat([torch.matmul(frames[..., :2, :2], _rotation(rad2deg(ang))), frames[..., :2, 2:]], dim=3).contiguous()
+        d = descriptor.describe(extract(frames)[:, :, 0])
+        desc[:, j0:j0 + step] = d.view(n, -1, 128)
+    desc.masked_fill_(dead[..., None], 0.0)
+    angles.masked_fill_(dead, 0.0)
+    return desc, angles
+
+
 def describe_keypoints(images, kpts, count=None, scale=12.0, lafs=None, orientation=False, patch_size=32, num_ang_bins=8,
-                       num_spatial_bins=4, rootsift=True, clipval=0.2, pyramid=False):
+                       num_spatial_bins=4, rootsift=True, clipval=0.2, pyramid=False, descriptor=None):
     """SIFT descriptors of the keypoints of a batch of images in one call (rr_describe_keypoints):
     the patch of ``extract_patches_simple`` (``cirtorch/features/laf.py``), optionally the dominant
     gradient orientation of ``LAFOrienter`` (``cirtorch/features/orientation.py``, 36 bins) and the
@@ -508,10 +570,27 @@ def describe_keypoints(images, kpts, count=None, scale=12.0, lafs=None, orientat
     the last level, where the reference leaves a zero patch.  Frames of level 0 give the same bits
     either way.  float64 arithmetic rounded once: bit-identical run to run and independent of the
     batch.  No patch is written to memory and nothing waits for the host: graph-capturable for
-    fixed shapes.  No gradients."""
+    fixed shapes.  No gradients.
+
+    descriptor=None is the SIFT descriptor above.  A ``cirtorch.features.HardNet`` or ``SOSNet``
+    instance (on the GPU, in eval mode) describes the same frames instead: desc is then float32
+    [B, N, 128] from rr_patchnet_describe (fp16 operands, float32 accumulation), the patches are those
+    of ``extract_patches_simple`` (``extract_patches_from_pyramid`` with pyramid=True) at patch_size
+    32 -- any other size raises --, orientation=True estimates the angle on the upright frame's patch
+    (rr_patch_orientation) and describes the frame turned by it.  The patches of at most 16384
+    keypoints are held at a time; dead slots are masked on the device; nothing waits for the host.
+    The SIFT arguments are ignored."""
     if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] not in (1, 3):
         raise ValueError("describe_keypoints: images are [B, 1, H, W] or [B, 3, H, W], got %s"
                          % (tuple(images.shape) if torch.is_tensor(images) else type(images),))
+    if descriptor is not None:
+        from .features.patchnet import PatchNet
+        if not isinstance(descriptor, PatchNet):
+            raise TypeError("describe_keypoints: descriptor is None (SIFT), a HardNet or a SOSNet, got %s" % type(descriptor))
+        if int(patch_size) != 32:
+            raise ValueError("describe_keypoints: %s takes 32 x 32 patches, got patch_size = %r"
+                             % (type(descriptor).__name__, patch_size))
+        return _describe_learned(images, kpts, count, float(scale), lafs, bool(orientation), bool(pyramid), descriptor)
     return _ops.describe_keypoints(images, kpts, count, float(scale), lafs, bool(orientation), 36, int(patch_size),
                                    int(num_ang_bins), int(num_spatial_bins), bool(rootsift), float(clipval),
                                    pyramid=bool(pyramid))

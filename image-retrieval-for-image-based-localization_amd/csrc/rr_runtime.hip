@@ -433,12 +433,22 @@ int rr_device_arch(char* buf, int buflen) {
 }
 
 int rr_set_tuning(int key, int value) {
+    if (key >= RR_TUNE_SIZE_BASE && key < RR_TUNE_SIZE_BASE + TUNE_NSIZEKEYS) {
+        if (value < 1) return fail(RR_EINVAL, "rr_set_tuning: a size key must be >= 1");
+        g_tune.*TUNE_SIZE_KEYS[key - RR_TUNE_SIZE_BASE].member = value;
+        return RR_OK;
+    }
     if (key < 0 || key >= TUNE_NKEYS) return fail(RR_EINVAL, "rr_set_tuning: unknown key");
     const char* err = tune_store(g_tune, key, value);
     return err ? fail(RR_EINVAL, err) : RR_OK;
 }
 
 int rr_get_tuning(int key, int* value) {
+    if (key >= RR_TUNE_SIZE_BASE && key < RR_TUNE_SIZE_BASE + TUNE_NSIZEKEYS) {
+        if (!value) return fail(RR_EINVAL, "rr_get_tuning: null value");
+        *value = g_tune.*TUNE_SIZE_KEYS[key - RR_TUNE_SIZE_BASE].member;
+        return RR_OK;
+    }
     if (key < 0 || key >= TUNE_NKEYS) return fail(RR_EINVAL, "rr_get_tuning: unknown key");
     if (!value) return fail(RR_EINVAL, "rr_get_tuning: null value");
     *value = g_tune.*TUNE_KEYS[key].member;

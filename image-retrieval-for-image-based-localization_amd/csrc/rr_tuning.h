@@ -27,6 +27,7 @@ struct Tuning {
     int wres = 2;
     int pair_mid = 1;
     int wres_ring = 1;
+    int patchnet_chunk = 16384;  // a size key (TUNE_SIZE_KEYS)
     // RR_KNN_FUSED=0 in the environment pins knn_fused to 0 for the process
     bool knn_fused_env_off = false;
 
@@ -70,5 +71,13 @@ inline constexpr TuneKey TUNE_KEYS[] = {
 };
 constexpr int TUNE_NKEYS = sizeof(TUNE_KEYS) / sizeof(TUNE_KEYS[0]);
 static_assert(TUNE_NKEYS == RR_TUNE_WRES_RING + 1, "one TUNE_KEYS row per rr_tune_key");
+
+// indexed by rr_tune_size_key - RR_TUNE_SIZE_BASE: the keys that set a length (and with it a
+// workspace size) instead of choosing a kernel; every value must be >= 1
+inline constexpr TuneKey TUNE_SIZE_KEYS[] = {
+    {&Tuning::patchnet_chunk, nullptr},
+};
+constexpr int TUNE_NSIZEKEYS = sizeof(TUNE_SIZE_KEYS) / sizeof(TUNE_SIZE_KEYS[0]);
+static_assert(TUNE_NSIZEKEYS == RR_TUNE_PATCHNET_CHUNK - RR_TUNE_SIZE_BASE + 1, "one TUNE_SIZE_KEYS row per rr_tune_size_key");
 
 }  // namespace rr

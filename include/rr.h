@@ -1001,6 +1001,80 @@ size_t rr_laf_affine_shape_workspace_bytes(int n, int c, int h, int w, int npts,
 int rr_laf_affine_shape(const void* x, int n, int c, int h, int w, int u8, const float* lafs, const int* count, int npts, int ps,
                         double eps, float* lafs_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Learned patch descriptors (rr_patchnet.hip): HardNet and SOSNet on 32 x 32 patches in eval mode.
+ * Replaces HardNet.forward / HardNet._normalize_input of cirtorch/features/hardnet.py:12-76 and
+ * SOSNet.forward of cirtorch/features/sosnet.py:9-58 (nn.Conv2d, nn.BatchNorm2d(affine=False),
+ * nn.ReLU, nn.InstanceNorm2d, nn.LocalResponseNorm, F.normalize; nn.Dropout is the identity).
+ *
+ * The shared trunk is seven bias-free convolutions, each followed by BatchNorm in eval mode,
+ * y = (x - running_mean) / sqrt(running_var + 1e-5), and, layers 1 .. 6, by ReLU:
+ *   layer   1        2         3          4         5          6           7
+ *   cin     1        32        32         64        64         128         128
+ *   cout    32       32        64         64        128        128         128
+ *   kernel  3x3 p1   3x3 p1    3x3 p1 s2  3x3 p1    3x3 p1 s2  3x3 p1      8x8 p0
+ *   map     32x32    32x32     16x16      16x16     8x8        8x8         1x1
+ * The input of layer 1 is the patch normalised by its own statistics (mean m over its 1024 pixels):
+ *   RR_PATCHNET_HARDNET  (x - m) / (sd + 1e-6),  sd = sqrt(sum (x - m)^2 / 1023)  (unbiased)
+ *   RR_PATCHNET_SOSNET   (x - m) / sqrt(sum (x - m)^2 / 1024 + 1e-5)              (InstanceNorm2d)
+ * and the descriptor is, with f the 128 values after layer 7's BatchNorm:
+ *   RR_PATCHNET_HARDNET  f / max(|f|_2, 1e-12)                                    (F.normalize)
+ *   RR_PATCHNET_SOSNET   v / |v|_2 with v = f + 1e-10, no eps.  That is LocalResponseNorm(256,
+ *                        alpha=256, beta=0.5, k=0) of v: over 128 channels the window of 256 covers
+ *                        every channel, and alpha times the averaged sum is the plain sum of squares.
+ *
+ * Precision: fp16 operands, float32 accumulation (v_mfma_f32_16x16x32_f16).  Where a value is rounded:
+ *  - rr_patchnet_pack rounds every weight once, float32 -> fp16 (nearest even), as given: BatchNorm is
+ *    not folded into the weights.  Per channel scale = float32(1 / sqrt(float64(var) + 1e-5)) and
+ *    shift = float32(-float64(mean) * (1 / sqrt(float64(var) + 1e-5))).
+ *  - the patch statistics are float64 sums in one fixed order (two pixels per thread, the xor
+ *    butterfly of a wave, the eight waves in ascending order); the normalised pixel is the float64
+ *    quotient rounded once to fp16.
+ *  - a layer's output pixel is float32 acc over K in the fixed order (tap ascending, then 32-channel
+ *    chunk ascending; layer 1: taps ascending, fmaf), then fmaf(acc, scale, shift) in float32, then
+ *    max(., 0), rounded once to fp16.  Layers 1 .. 6 do this.
+ *  - layer 7 accumulates in float32 over K = 8192 in the order of the map ((y, x) ascending, then
+ *    channel) in eight slices of 1024 (one per wave), each from zero; the slices are added in
+ *    ascending order.  Its BatchNorm is fmaf(acc, scale, shift) in float32, the + 1e-10 (SOSNet), the sum of
+ *    squares (channels 16 n + c over n ascending, then the xor butterfly over c), the square root
+ *    and the quotient are float32.  The descriptor is float32.
+ * A descriptor depends on its own patch and the weights only: not on B, on the patch's position in
+ * the batch, on the chunk length or on the run (no atomics, fixed summation order).
+ *
+ * rr_patchnet_packed_bytes / rr_patchnet_pack: the seven weights [cout][cin][kh][kw] float32 and the
+ * seven running_mean / running_var [cout] float32 -- weights, means, vars are HOST arrays of 7 DEVICE
+ * pointers, layer 1 first -- into one device blob `packed` (16-byte aligned, at least
+ * rr_patchnet_packed_bytes() = 2,673,920 B): the fp16 weights of layers 1 .. 7, layer 1 as [tap][cout],
+ * layers 2 .. 7 as [tap * cin / 32 + chunk][cout][32] (layer 7's taps are the 64 pixels of the map, so
+ * its K order is the order in which the trunk writes the map), then float32 scale[576] and shift[576].
+ *
+ * rr_patchnet_trunk: patches [B][32][32] float32 (8-byte aligned) -> map [B][8][8][128] fp16, the
+ * output of layer 6 (16-byte aligned).  One launch, one workgroup per patch; the normalised patch
+ * and the maps of layers 1 .. 5 stay in LDS (two regions of one zero-padded 34 x 34 x 32 fp16 map,
+ * 147,968 B; later maps reuse them), layer 1 is vector work and layers 2 .. 6 are implicit GEMMs of
+ * M = pixels, N = cout, K = 9 cin whose weights stream from the L2.
+ * rr_patchnet_head: map -> desc [B][128] float32: layer 7 as a [B][8192] x [8192][128] GEMM, a workgroup
+ * per 16 patches (its 8 waves split K), its BatchNorm and the descriptor normalisation; the 2 MiB of
+ * weights are read once per 16 patches, from the L2.
+ * rr_patchnet_describe: the two in chunks of RR_TUNE_PATCHNET_CHUNK patches (trunk on a chunk, then
+ * head on that chunk), so the workspace -- the maps of one chunk, 16 KiB a patch -- is bounded
+ * whatever B is; the result has the bits of the chain of the two entries.  workspace: at least
+ * rr_patchnet_workspace_bytes(B), which reads the chunk length in force when it is called.
+ * Errors, before anything is enqueued: B < 0, an unknown variant, null pointers, a misaligned
+ * pointer (RR_EINVAL), a short packed buffer or workspace (RR_ENOSPACE).  B == 0 returns RR_OK and
+ * launches nothing.  Nothing waits for the host (graph-capturable).
+ * Not built: an fp32 or bf16 mode of the net, HardNet8, AffNet, OriNet, training (batch statistics,
+ * dropout, a backward pass), pretrained files, and patch sampling fused into the trunk. */
+#define RR_PATCHNET_HARDNET 0
+#define RR_PATCHNET_SOSNET 1
+size_t rr_patchnet_packed_bytes(void);
+int rr_patchnet_pack(const float* const* weights, const float* const* means, const float* const* vars, void* packed,
+                     size_t packed_bytes, void* stream);
+size_t rr_patchnet_workspace_bytes(long long B);
+int rr_patchnet_trunk(const float* patches, long long B, int variant, const void* packed, void* map, void* stream);
+int rr_patchnet_head(const void* map, long long B, int variant, const void* packed, float* desc, void* stream);
+int rr_patchnet_describe(const float* patches, long long B, int variant, const void* packed, float* desc, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 /* Full ranking for any database size: out_idx[q][r] = the r-th database row of
  * query q by (float64 score desc, index asc) — np.argsort(-np.dot(vecs.T, qvecs),
  * axis=0) of scripts/test.py:247-248 as [nq][n] (rr_knn_topk ranks k <= 8192).
@@ -1084,6 +1158,11 @@ int rr_rank_full(const float* db_f32, long long n, const float* q_f32, int nq, i
  *                        conv1) keep 5 (K = 256) / 3 (K = 512) activation tiles in flight; 0: two
  *                        (same results bit for bit)
  *
+ * Size keys (enum rr_tune_size_key, from RR_TUNE_SIZE_BASE): a length, not a kernel choice; a value
+ * below 1 is an error.  A workspace-size function reads the value in force when it is called.
+ *   RR_TUNE_PATCHNET_CHUNK  patches per trunk + head pair of rr_patchnet_describe (default 16384:
+ *                        256 MiB of maps); the result does not depend on it
+ *
  * Environment variables without a key (A/B switches, read where they apply):
  *   RR_GEMM_PRIO=1       raised wave priority for the second half of k_igemm's waves
  *   RR_GEMM8S_R=3|6      K-steps in flight per wave in k_gemm8s (default 4)
@@ -1099,6 +1178,7 @@ enum rr_tune_key { RR_TUNE_GEMM_CONFIG = 0, RR_TUNE_GEMM_STAGES = 1, RR_TUNE_GEM
                    RR_TUNE_KNN_FUSED = 9, RR_TUNE_CONV3_PIPE = 10,
                    RR_TUNE_STEM = 11, RR_TUNE_STREAM_XCD = 12, RR_TUNE_CONV3S = 13,
                    RR_TUNE_WRES = 14, RR_TUNE_PAIR_MID = 15, RR_TUNE_WRES_RING = 16 };
+enum rr_tune_size_key { RR_TUNE_SIZE_BASE = 32, RR_TUNE_PATCHNET_CHUNK = 32 };
 int rr_set_tuning(int key, int value);
 int rr_get_tuning(int key, int* value);
 
