@@ -90,11 +90,12 @@ __device__ __forceinline__ void lds_zero(unsigned char* p, int bytes) {
 // 16 consecutive pixels of the row-major output), N = COUT in tiles of 16, K = 9 taps x CIN / 32 steps
 // in (tap, chunk) order.  A job is MB pixel tiles x one channel tile; (WO * WO / 16 / MB) * (COUT / 16)
 // is 8 for every layer, one job per wave.  in: zero-padded [(WO * S + 2)][(WO * S + 2)][CIN] fp16.
-// out: zero-padded [(WO + 2)][(WO + 2)][COUT] fp16 in LDS, or the [WO][WO][COUT] map in memory (TO_MEM).
+// out: zero-padded [(WO + 2)][(WO + 2)][COUT] fp16 in LDS, or the [WO][WO][COUT] map in memory (TO_MEM),
+// which is NaN in every entry when `bad` (a non-finite patch).
 template <int CIN, int COUT, int WO, int S, int MB, bool TO_MEM>
 __device__ __forceinline__ void conv3_layer(const unsigned char* in, unsigned char* out, f16_t* gout,
                                             const f16_t* __restrict__ w, const float* __restrict__ scale,
-                                            const float* __restrict__ shift) {
+                                            const float* __restrict__ shift, bool bad = false) {
     constexpr int WP = WO * S + 2, NCC = CIN / 32, NT = COUT / 16, MT = WO * WO / 16;
     static_assert(MT % MB == 0 && (MT / MB) * NT == T_TB / 64, "one job per wave");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -142,7 +143,7 @@ __device__ __forceinline__ void conv3_layer(const unsigned char* in, unsigned ch
             const int p = (mblk * MB + mb) * 16 + fq * 4 + r;
             const f16_t v = (f16_t)fmaxf(fmaf(acc[mb][r], sc, sh), 0.f);
             if (TO_MEM)
-                gout[p * COUT + c] = v;
+                gout[p * COUT + c] = bad ? (f16_t)__builtin_nanf("") : v;
             else
                 reinterpret_cast<f16_t*>(out)[((p / WO + 1) * (WO + 2) + p % WO + 1) * COUT + c] = v;
         }
@@ -172,6 +173,15 @@ __global__ void __launch_bounds__(T_TB) k_patchnet_trunk(const float* __restrict
         s = 0.0;
 #pragma unroll
         for (int i = 0; i < 8; ++i) s += red[i];
+        // A NaN or an infinite pixel makes this sum non-finite (1024 finite floats cannot), and then every
+        // normalised pixel is NaN.  fmaxf in the ReLUs below would turn that into zeros and give the patch
+        // the descriptor of the BatchNorm shifts, so the patch gets its all-NaN map here (rr.h).  s is the
+        // same in every thread: the whole block takes the branch.
+        // A NaN or an infinite pixel makes this sum non-finite (1024 finite floats cannot), and then every
+        // normalised pixel is NaN.  fmaxf in the ReLUs below turns that into zeros, which would give the
+        // patch the descriptor of the BatchNorm shifts; layer 6 stores NaN instead (rr.h).  The same in
+        // every thread, and no control flow depends on it.
+        const bool bad = !isfinite(s);
         const double mean = s / 1024.0;
         const double d0 = (double)xv.x - mean, d1 = (double)xv.y - mean;
         __syncthreads();   // every thread has read red
@@ -237,7 +247,7 @@ __global__ void __launch_bounds__(T_TB) k_patchnet_trunk(const float* __restrict
         conv3_layer<64, 128, 8, 2, 4, false>(rb, ra, nullptr, wp + pn_w_off(4), scale + pn_c_off(4), shift + pn_c_off(4));
         __syncthreads();
         conv3_layer<128, 128, 8, 1, 4, true>(ra, nullptr, maps + patch * PN_MAP, wp + pn_w_off(5), scale + pn_c_off(5),
-                                              shift + pn_c_off(5));
+                                              shift + pn_c_off(5), bad);
     }
 }
 

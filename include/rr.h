@@ -1039,6 +1039,12 @@ int rr_laf_affine_shape(const void* x, int n, int c, int h, int w, int u8, const
  *    and the quotient are float32.  The descriptor is float32.
  * A descriptor depends on its own patch and the weights only: not on B, on the patch's position in
  * the batch, on the chunk length or on the run (no atomics, fixed summation order).
+ * Non-finite input: a patch with a NaN or an infinite pixel has non-finite statistics, so every
+ * normalised pixel is NaN and the reference modules return NaN in every entry.  So do these entries:
+ * the trunk sees it in the float64 sum of the pixels (finite for 1024 finite floats) and stores NaN
+ * (0x7E00) in every entry of the map in place of layer 6's outputs, because the max(., 0) of the
+ * layers drops a NaN; the head carries the NaN to all 128 entries.  No other patch of the batch is affected (a row of the head's GEMM is one
+ * patch).  A NaN descriptor matches nothing in rr_match_pairs.
  *
  * rr_patchnet_packed_bytes / rr_patchnet_pack: the seven weights [cout][cin][kh][kw] float32 and the
  * seven running_mean / running_var [cout] float32 -- weights, means, vars are HOST arrays of 7 DEVICE

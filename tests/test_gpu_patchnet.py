@@ -71,6 +71,20 @@ def test_descriptors_against_reference(cuda, fix, nets, x129, full, variant, B):
 
 
 @pytest.mark.parametrize("variant", NC.VARIANTS)
+def test_descriptors_against_the_restatement(cuda, full, variant):
+    """against patchnet_cases.quantised_net (fp16 at the rounding points of rr.h, float64 elsewhere), within 4 x
+    what a float32 accumulation moves it by: the difference of quantised_net and quantised_net_f32 over the
+    same 129 patches, measured by make_golden_patchnet_edges.py (1.18e-4 / 1.20e-4) and re-measured by
+    test_host_patchnet_edges.py.  Less than half the tolerance against the float64 reference above."""
+    tol = float(golden("patchnet_edges.npz")[variant + "_f32_tol"])
+    want = NC.quantised_net(NC.patches(), NC.net_params(NC.SEEDS[variant]), variant)[0]
+    diff = np.abs(full[variant].cpu().numpy().astype(np.float64) - want).max()
+    print("%s: max |GPU - quantised_net| %.3e (tol %.3e)" % (variant, diff, tol))
+    assert tol < 5e-4
+    assert diff <= tol
+
+
+@pytest.mark.parametrize("variant", NC.VARIANTS)
 def test_trunk_map_against_reference(cuda, fix, nets, x129, variant):
     from cirtorch import _ops
     idx = list(NC.MAP_PATCHES)
