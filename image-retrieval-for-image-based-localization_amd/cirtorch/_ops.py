@@ -710,6 +710,36 @@ VERIFY_MODELS = {"homography": ("rr_verify_workspace_bytes", "rr_verify_pairs"),
                  "fundamental": ("rr_verify_epipolar_workspace_bytes", "rr_verify_pairs_epipolar")}
 
 
+def _pair_args(prefix, kp1, off1, kp2, off2, match, max_n1):
+    """the checks of every entry on float32 keypoints, offsets and a match list -> rows1, rows2, P, max_n1"""
+    if kp1.dim() != 2 or kp2.dim() != 2 or kp1.shape[1] != 2 or kp2.shape[1] != 2:
+        raise RuntimeError("%s: keypoints must be [rows, 2], got %s and %s" % (prefix, tuple(kp1.shape), tuple(kp2.shape)))
+    if kp1.dtype != torch.float32 or kp2.dtype != torch.float32 or not kp1.is_contiguous() or not kp2.is_contiguous():
+        raise RuntimeError("%s: keypoints must be contiguous float32 rows" % prefix)
+    if off1.dtype != torch.int64 or off2.dtype != torch.int64 or off1.numel() != off2.numel() or off1.numel() < 1:
+        raise RuntimeError("%s: offsets must be int64 [P + 1] for both sides" % prefix)
+    rows1, rows2, npairs = kp1.shape[0], kp2.shape[0], off1.numel() - 1
+    if match.dtype != torch.int64 or match.dim() != 1 or match.shape[0] != rows1 or not match.is_contiguous():
+        raise RuntimeError("%s: match must be contiguous int64 [rows1]" % prefix)
+    return rows1, rows2, npairs, rows1 if max_n1 is None else min(int(max_n1), rows1)
+
+
+def _point_set_args(prefix, pts1, pts2, off, weights=None, mats=(), names=None, mat_shape=None):
+    """the checks of every entry on float64 point sets [rows, 2] x 2 with offsets [P + 1] -> rows, P.
+    weights: per-row float64 or None; mats: per-pair float64 [P, *mat_shape] the messages call `names`"""
+    if pts1.dim() != 2 or pts1.shape[1] != 2 or pts1.shape != pts2.shape:
+        raise RuntimeError("%s: points must be [rows, 2] on both sides, got %s and %s" % (prefix, tuple(pts1.shape), tuple(pts2.shape)))
+    if any(t.dtype != torch.float64 or not t.is_contiguous() for t in (pts1, pts2) + tuple(mats)):
+        raise RuntimeError("%s: points%s must be contiguous float64%s" % (prefix, " and " + names if mats else "", "" if mats else " rows"))
+    rows, npairs = pts1.shape[0], off.numel() - 1
+    if weights is not None and (weights.dtype != torch.float64 or weights.shape != (rows,) or not weights.is_contiguous()):
+        raise RuntimeError("%s: weights must be contiguous float64 [rows]" % prefix)
+    if off.dtype != torch.int64 or off.numel() < 1 or any(tuple(m.shape) != (npairs,) + tuple(mat_shape) for m in mats):
+        raise RuntimeError("%s: offsets int64 [P + 1] and %s [P, %d, %d]" % ((prefix, names) + tuple(mat_shape)) if mats
+                           else "%s: offsets must be int64 [P + 1]" % prefix)
+    return rows, npairs
+
+
 def verify_pairs(kp1, off1, kp2, off2, match, th=3.0, iters=1024, refine=2, seed=0, max_n1=None, covered=False,
                  model="homography"):
     """rr_verify_pairs (model "homography") / rr_verify_pairs_epipolar ("fundamental"): kp1 [rows1, 2],
@@ -718,16 +748,7 @@ def verify_pairs(kp1, off1, kp2, off2, match, th=3.0, iters=1024, refine=2, seed
     covered=True: the pairs cover every side-1 row (the mask is not pre-filled with 0).  No synchronisation."""
     ws_bytes, entry = VERIFY_MODELS[model]
     E.require_gpu(kp1, off1, kp2, off2, match)
-    if kp1.dim() != 2 or kp2.dim() != 2 or kp1.shape[1] != 2 or kp2.shape[1] != 2:
-        raise RuntimeError("verify: keypoints must be [rows, 2], got %s and %s" % (tuple(kp1.shape), tuple(kp2.shape)))
-    if kp1.dtype != torch.float32 or kp2.dtype != torch.float32 or not kp1.is_contiguous() or not kp2.is_contiguous():
-        raise RuntimeError("verify: keypoints must be contiguous float32 rows")
-    if off1.dtype != torch.int64 or off2.dtype != torch.int64 or off1.numel() != off2.numel() or off1.numel() < 1:
-        raise RuntimeError("verify: offsets must be int64 [P + 1] for both sides")
-    rows1, rows2, npairs = kp1.shape[0], kp2.shape[0], off1.numel() - 1
-    if match.dtype != torch.int64 or match.dim() != 1 or match.shape[0] != rows1 or not match.is_contiguous():
-        raise RuntimeError("verify: match must be contiguous int64 [rows1]")
-    max_n1 = rows1 if max_n1 is None else min(int(max_n1), rows1)
+    rows1, rows2, npairs, max_n1 = _pair_args("verify", kp1, off1, kp2, off2, match, max_n1)
     dev = kp1.device
     inliers = torch.empty(npairs, dtype=torch.int32, device=dev)   # written for every pair
     H = torch.empty((npairs, 3, 3), dtype=torch.float64, device=dev)
@@ -740,44 +761,27 @@ def verify_pairs(kp1, off1, kp2, off2, match, th=3.0, iters=1024, refine=2, seed
     return inliers, H, mask
 
 
+def _fit_batch(entry, prefix, pts1, pts2, weights, off):
+    """one of the two batched fits: pts1, pts2 float64 [rows, 2], weights float64 [rows] or None,
+    device int64 offsets [P + 1] -> float64 [P, 3, 3].  No synchronisation."""
+    E.require_gpu(pts1, pts2, weights, off)
+    rows, npairs = _point_set_args(prefix, pts1, pts2, off, weights)
+    M = torch.empty((npairs, 3, 3), dtype=torch.float64, device=pts1.device)
+    E.check(getattr(E.lib(), entry)(E.ptr(pts1), E.ptr(pts2), E.ptr(weights), E.ptr(off), rows, npairs, E.ptr(M),
+                                    E.ptr(None), 0, _st()), entry)
+    return M
+
+
 def homography_dlt(pts1, pts2, weights, off):
     """rr_homography_dlt: pts1, pts2 float64 [rows, 2], weights float64 [rows] or None, device int64
     offsets [P + 1] -> H float64 [P, 3, 3] (find_homography_dlt per point set).  No synchronisation."""
-    E.require_gpu(pts1, pts2, weights, off)
-    if pts1.dim() != 2 or pts1.shape[1] != 2 or pts1.shape != pts2.shape:
-        raise RuntimeError("dlt: points must be [rows, 2] on both sides, got %s and %s" % (tuple(pts1.shape), tuple(pts2.shape)))
-    if pts1.dtype != torch.float64 or pts2.dtype != torch.float64 or not pts1.is_contiguous() or not pts2.is_contiguous():
-        raise RuntimeError("dlt: points must be contiguous float64 rows")
-    rows = pts1.shape[0]
-    if weights is not None and (weights.dtype != torch.float64 or weights.shape != (rows,) or not weights.is_contiguous()):
-        raise RuntimeError("dlt: weights must be contiguous float64 [rows]")
-    if off.dtype != torch.int64 or off.numel() < 1:
-        raise RuntimeError("dlt: offsets must be int64 [P + 1]")
-    npairs = off.numel() - 1
-    H = torch.empty((npairs, 3, 3), dtype=torch.float64, device=pts1.device)
-    E.check(E.lib().rr_homography_dlt(E.ptr(pts1), E.ptr(pts2), E.ptr(weights), E.ptr(off), rows, npairs, E.ptr(H),
-                                      E.ptr(None), 0, _st()), "rr_homography_dlt")
-    return H
+    return _fit_batch("rr_homography_dlt", "dlt", pts1, pts2, weights, off)
 
 
 def fundamental_dlt(pts1, pts2, weights, off):
     """rr_fundamental_dlt: the arguments of homography_dlt -> F float64 [P, 3, 3] (find_fundamental
     per point set; zeros for a set of fewer than 8 points).  No synchronisation."""
-    E.require_gpu(pts1, pts2, weights, off)
-    if pts1.dim() != 2 or pts1.shape[1] != 2 or pts1.shape != pts2.shape:
-        raise RuntimeError("fundamental: points must be [rows, 2] on both sides, got %s and %s" % (tuple(pts1.shape), tuple(pts2.shape)))
-    if pts1.dtype != torch.float64 or pts2.dtype != torch.float64 or not pts1.is_contiguous() or not pts2.is_contiguous():
-        raise RuntimeError("fundamental: points must be contiguous float64 rows")
-    rows = pts1.shape[0]
-    if weights is not None and (weights.dtype != torch.float64 or weights.shape != (rows,) or not weights.is_contiguous()):
-        raise RuntimeError("fundamental: weights must be contiguous float64 [rows]")
-    if off.dtype != torch.int64 or off.numel() < 1:
-        raise RuntimeError("fundamental: offsets must be int64 [P + 1]")
-    npairs = off.numel() - 1
-    F = torch.empty((npairs, 3, 3), dtype=torch.float64, device=pts1.device)
-    E.check(E.lib().rr_fundamental_dlt(E.ptr(pts1), E.ptr(pts2), E.ptr(weights), E.ptr(off), rows, npairs, E.ptr(F),
-                                       E.ptr(None), 0, _st()), "rr_fundamental_dlt")
-    return F
+    return _fit_batch("rr_fundamental_dlt", "fundamental", pts1, pts2, weights, off)
 
 
 EPI_KINDS = {"sampson": E.RR_EPI_SAMPSON, "symmetrical": E.RR_EPI_SYMMETRICAL}
@@ -787,14 +791,7 @@ def epipolar_distance(pts1, pts2, F, off, kind, squared=True, eps=1e-8):
     """rr_epipolar_distance: pts1, pts2 float64 [rows, 2], F float64 [P, 3, 3], device int64 offsets
     [P + 1] covering every row -> float64 [rows].  No synchronisation."""
     E.require_gpu(pts1, pts2, F, off)
-    if pts1.dim() != 2 or pts1.shape[1] != 2 or pts1.shape != pts2.shape:
-        raise RuntimeError("epipolar distance: points must be [rows, 2] on both sides, got %s and %s"
-                           % (tuple(pts1.shape), tuple(pts2.shape)))
-    if any(t.dtype != torch.float64 or not t.is_contiguous() for t in (pts1, pts2, F)):
-        raise RuntimeError("epipolar distance: points and F must be contiguous float64")
-    if off.dtype != torch.int64 or off.numel() < 1 or tuple(F.shape) != (off.numel() - 1, 3, 3):
-        raise RuntimeError("epipolar distance: offsets int64 [P + 1] and F [P, 3, 3]")
-    rows, npairs = pts1.shape[0], off.numel() - 1
+    rows, npairs = _point_set_args("epipolar distance", pts1, pts2, off, mats=(F,), names="F", mat_shape=(3, 3))
     out = torch.empty(rows, dtype=torch.float64, device=pts1.device)
     E.check(E.lib().rr_epipolar_distance(E.ptr(pts1), E.ptr(pts2), E.ptr(F), E.ptr(off), rows, npairs, EPI_KINDS[kind],
                                          1 if squared else 0, float(eps), E.ptr(out), _st()), "rr_epipolar_distance")
@@ -813,21 +810,12 @@ def recover_pose(kp1, off1, kp2, off2, match, mask, F, K1, K2, max_n1=None, cove
     points3d float64 [rows1, 3], front_mask uint8 [rows1]).  covered=True: the pairs cover every
     side-1 row (the per-row outputs are not pre-filled with 0).  No synchronisation."""
     E.require_gpu(kp1, off1, kp2, off2, match, mask, F, K1, K2)
-    if kp1.dim() != 2 or kp2.dim() != 2 or kp1.shape[1] != 2 or kp2.shape[1] != 2:
-        raise RuntimeError("pose: keypoints must be [rows, 2], got %s and %s" % (tuple(kp1.shape), tuple(kp2.shape)))
-    if kp1.dtype != torch.float32 or kp2.dtype != torch.float32 or not kp1.is_contiguous() or not kp2.is_contiguous():
-        raise RuntimeError("pose: keypoints must be contiguous float32 rows")
-    if off1.dtype != torch.int64 or off2.dtype != torch.int64 or off1.numel() != off2.numel() or off1.numel() < 1:
-        raise RuntimeError("pose: offsets must be int64 [P + 1] for both sides")
-    rows1, rows2, npairs = kp1.shape[0], kp2.shape[0], off1.numel() - 1
-    if match.dtype != torch.int64 or match.dim() != 1 or match.shape[0] != rows1 or not match.is_contiguous():
-        raise RuntimeError("pose: match must be contiguous int64 [rows1]")
+    rows1, rows2, npairs, max_n1 = _pair_args("pose", kp1, off1, kp2, off2, match, max_n1)
     if mask is not None:
         if mask.dtype not in (torch.uint8, torch.bool) or tuple(mask.shape) != (rows1,) or not mask.is_contiguous():
             raise RuntimeError("pose: mask must be contiguous uint8 or bool [rows1]")
     for m, what in ((F, "F"), (K1, "K1"), (K2, "K2")):
         _mat33(m, npairs, what)
-    max_n1 = rows1 if max_n1 is None else min(int(max_n1), rows1)
     dev = kp1.device
     new = torch.empty if covered and npairs else torch.zeros
     R = torch.empty((npairs, 3, 3), dtype=torch.float64, device=dev)   # written for every pair
@@ -847,14 +835,7 @@ def triangulate_points(pts1, pts2, P1, P2, off):
     """rr_triangulate_points: pts1, pts2 float64 [rows, 2], P1, P2 float64 [P, 3, 4], device int64
     offsets [P + 1] covering every row -> X float64 [rows, 3].  No synchronisation."""
     E.require_gpu(pts1, pts2, P1, P2, off)
-    if pts1.dim() != 2 or pts1.shape[1] != 2 or pts1.shape != pts2.shape:
-        raise RuntimeError("triangulate: points must be [rows, 2] on both sides, got %s and %s"
-                           % (tuple(pts1.shape), tuple(pts2.shape)))
-    if any(x.dtype != torch.float64 or not x.is_contiguous() for x in (pts1, pts2, P1, P2)):
-        raise RuntimeError("triangulate: points and projections must be contiguous float64")
-    if off.dtype != torch.int64 or off.numel() < 1 or tuple(P1.shape) != (off.numel() - 1, 3, 4) or P2.shape != P1.shape:
-        raise RuntimeError("triangulate: offsets int64 [P + 1] and projections [P, 3, 4]")
-    rows, npairs = pts1.shape[0], off.numel() - 1
+    rows, npairs = _point_set_args("triangulate", pts1, pts2, off, mats=(P1, P2), names="projections", mat_shape=(3, 4))
     X = torch.empty((rows, 3), dtype=torch.float64, device=pts1.device)
     E.check(E.lib().rr_triangulate_points(E.ptr(pts1), E.ptr(pts2), E.ptr(P1), E.ptr(P2), E.ptr(off), rows, npairs,
                                           E.ptr(X), _st()), "rr_triangulate_points")

@@ -49,6 +49,31 @@ inline int check_launch(const char* what) {
     return RR_OK;
 }
 
+// Argument checks of the pair-geometry entries (rr_verify.hip, rr_epipolar.hip, rr_pose.hip); w: the entry's name.
+// what every entry on keypoints, offsets and a match list checks
+inline int check_pair_args(const std::string& w, const float* kp1, const long long* off1, long long rows1, const float* kp2,
+                           const long long* off2, long long rows2, const long long* match, int npairs, int max_n1) {
+    if (npairs < 0 || rows1 < 0 || rows2 < 0 || max_n1 < 0) return fail(RR_EINVAL, w + ": negative size");
+    if (!off1 || !off2) return fail(RR_EINVAL, w + ": null offsets");
+    if ((rows1 > 0 && (!kp1 || !match)) || (rows2 > 0 && !kp2)) return fail(RR_EINVAL, w + ": null keypoints or match");
+    if ((((uintptr_t)kp1) & 7) || (((uintptr_t)kp2) & 7)) return fail(RR_EINVAL, w + ": keypoints must be 8-byte aligned");
+    if (max_n1 > rows1) return fail(RR_EINVAL, w + ": max_n1 exceeds the row count");
+    if (rows1 > 0x7fffffffll || rows2 > 0x7fffffffll) return fail(RR_EINVAL, w + ": too many rows");
+    return RR_OK;
+}
+
+// what every entry on caller-supplied float64 point sets checks; with_out: the entry writes one value per row to out
+inline int check_point_set_args(const std::string& w, const double* pts1, const double* pts2, const long long* off,
+                                long long rows, int npairs, bool with_out = false, const void* out = nullptr) {
+    if (npairs < 0 || rows < 0) return fail(RR_EINVAL, w + ": negative size");
+    if (!off) return fail(RR_EINVAL, w + ": null offsets");
+    if (rows > 0 && (!pts1 || !pts2 || (with_out && !out)))
+        return fail(RR_EINVAL, w + (with_out ? ": null points or output" : ": null points"));
+    if ((((uintptr_t)pts1) & 15) || (((uintptr_t)pts2) & 15)) return fail(RR_EINVAL, w + ": points must be 16-byte aligned");
+    if (rows > 0x7fffffffll) return fail(RR_EINVAL, w + ": too many rows");
+    return RR_OK;
+}
+
 // bf16 stored as raw uint16 bits.
 typedef uint16_t bf16_t;
 typedef _Float16 f16_t;  // IEEE binary16 (kNN screening copies)

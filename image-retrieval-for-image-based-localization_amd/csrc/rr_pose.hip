@@ -373,12 +373,8 @@ int rr_recover_pose(const float* kp1, const long long* off1, long long rows1, co
     (void)workspace;
     (void)workspace_bytes;
     const std::string w("rr_recover_pose");
-    if (npairs < 0 || rows1 < 0 || rows2 < 0 || max_n1 < 0) return fail(RR_EINVAL, w + ": negative size");
-    if (!off1 || !off2) return fail(RR_EINVAL, w + ": null offsets");
-    if ((rows1 > 0 && (!kp1 || !match)) || (rows2 > 0 && !kp2)) return fail(RR_EINVAL, w + ": null keypoints or match");
-    if ((((uintptr_t)kp1) & 7) || (((uintptr_t)kp2) & 7)) return fail(RR_EINVAL, w + ": keypoints must be 8-byte aligned");
-    if (max_n1 > rows1) return fail(RR_EINVAL, w + ": max_n1 exceeds the row count");
-    if (rows1 > 0x7fffffffll || rows2 > 0x7fffffffll) return fail(RR_EINVAL, w + ": too many rows");
+    const int rc = check_pair_args(w, kp1, off1, rows1, kp2, off2, rows2, match, npairs, max_n1);
+    if (rc) return rc;
     if (npairs > 0 && (!F || !K1 || !K2)) return fail(RR_EINVAL, w + ": null F, K1 or K2");
     if (npairs > 0 && (!R || !t || !E || !front)) return fail(RR_EINVAL, w + ": null output");
     if (npairs > 0 && rows1 > 0 && (!points3d || !front_mask)) return fail(RR_EINVAL, w + ": null output");
@@ -392,11 +388,8 @@ int rr_recover_pose(const float* kp1, const long long* off1, long long rows1, co
 int rr_triangulate_points(const double* pts1, const double* pts2, const double* P1, const double* P2, const long long* off,
                           long long rows, int npairs, double* X, void* stream) {
     const std::string w("rr_triangulate_points");
-    if (npairs < 0 || rows < 0) return fail(RR_EINVAL, w + ": negative size");
-    if (!off) return fail(RR_EINVAL, w + ": null offsets");
-    if (rows > 0 && (!pts1 || !pts2 || !X)) return fail(RR_EINVAL, w + ": null points or output");
-    if ((((uintptr_t)pts1) & 15) || (((uintptr_t)pts2) & 15)) return fail(RR_EINVAL, w + ": points must be 16-byte aligned");
-    if (rows > 0x7fffffffll) return fail(RR_EINVAL, w + ": too many rows");
+    const int rc = check_point_set_args(w, pts1, pts2, off, rows, npairs, true, X);
+    if (rc) return rc;
     if (npairs > 0 && (!P1 || !P2)) return fail(RR_EINVAL, w + ": null projection matrices");
     if (npairs == 0) return RR_OK;
     hipLaunchKernelGGL(k_triangulate, dim3((unsigned)(npairs < 65535 ? npairs : 65535)), dim3(V_TB), 0, as_stream(stream),

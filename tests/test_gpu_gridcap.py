@@ -9,14 +9,14 @@ test executes:
 
   test_match_pairs_and_top2_past_the_cap      k_match_top2 (s_o reused by the merge; no == 0 and row0 >= nq
                                               between ordinary pairs), k_match_final
-  test_dlt_and_fundamental_fits_past_the_cap  k_dlt_batch (DltLds), k_fund_batch (FundLds)
+  test_dlt_and_fundamental_fits_past_the_cap  k_fit_batch<Homography>, k_fit_batch<Fundamental> (FitLds<M>)
   test_epipolar_distances_past_the_cap        k_epi_distance
   test_triangulate_past_the_cap               k_triangulate (s_P)
   test_recover_pose_past_the_cap              k_recover_pose (PoseLds, s_cnt)
   test_essential_decompose_past_the_cap       k_essential_decompose (256 matrices per block)
-  test_verify_pairs_past_the_cap              k_verify_compact (s_w), k_verify_ransac / k_epi_ransac (s_rec behind
-                                              the barrier inside `if (m >= 4)` / `if (m >= 7)`: staged, unstaged and
-                                              skipped pairs in every order), k_verify_refit / k_epi_refit
+  test_verify_pairs_past_the_cap              k_verify_compact (s_w), k_ransac<M> for both models (s_rec behind the
+                                              barrier inside `if (m >= M::SAMPLE)`, 4 / 7: staged, unstaged and
+                                              skipped pairs in every order), k_refit<M> for both models
 
 Tolerances of the restatements are those of the modules they come from: indices, counts and masks exact (the
 margins are asserted in test_host_gridcap.py), matrices and points within 100 x the difference of two float64

@@ -11,7 +11,7 @@ CORNERS = np.array([[0.0, 0.0], [W, 0.0], [W, H_IMG], [0.0, H_IMG]])
 DET_EPS = 1e-6      # RR_VERIFY_DET_EPS
 W_EPS = 1e-8
 EPS = 1e-8
-STAGE = 1024        # records of the LDS stage of k_verify_ransac
+STAGE = 1024        # records of the LDS stage of the RANSAC kernel (V_STAGE)
 
 # ---------------------------------------------------------------- DLT cases (find_homography_dlt)
 # (B, N, weighted): N in {4, 5, 8, 50, 500}, B in {1, 3}; weighted cases zero some rows' weights
