@@ -110,6 +110,10 @@ _SIGS = {
                                   _vp, _sz, _vp], _i),
     "rr_fundamental_dlt": ([_vp, _vp, _vp, _vp, _ll, _i, _vp, _vp, _sz, _vp], _i),
     "rr_epipolar_distance": ([_vp, _vp, _vp, _vp, _ll, _i, _i, _i, _d, _vp, _vp], _i),
+    "rr_verify_essential_workspace_bytes": ([_ll, _i, _i], _sz),
+    "rr_verify_pairs_essential": ([_vp, _vp, _ll, _vp, _vp, _ll, _vp, _i, _i, _vp, _vp, _d, _i, _i, ctypes.c_ulonglong, _vp,
+                                   _vp, _vp, _vp, _sz, _vp], _i),
+    "rr_essential_5pt": ([_vp, _vp, _i, _vp, _vp, _vp], _i),
     "rr_recover_pose": ([_vp, _vp, _ll, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                          _vp], _i),
     "rr_triangulate_points": ([_vp, _vp, _vp, _vp, _vp, _ll, _i, _vp, _vp], _i),

@@ -707,7 +707,8 @@ def match_pairs(a, a_off, b, b_off, mode, th=0.8, max_n1=None, max_n2=None, cove
 
 # ---------------------------------------------------------------- spatial verification
 VERIFY_MODELS = {"homography": ("rr_verify_workspace_bytes", "rr_verify_pairs"),
-                 "fundamental": ("rr_verify_epipolar_workspace_bytes", "rr_verify_pairs_epipolar")}
+                 "fundamental": ("rr_verify_epipolar_workspace_bytes", "rr_verify_pairs_epipolar"),
+                 "essential": ("rr_verify_essential_workspace_bytes", "rr_verify_pairs_essential")}
 
 
 def _pair_args(prefix, kp1, off1, kp2, off2, match, max_n1):
@@ -741,21 +742,31 @@ def _point_set_args(prefix, pts1, pts2, off, weights=None, mats=(), names=None, 
 
 
 def verify_pairs(kp1, off1, kp2, off2, match, th=3.0, iters=1024, refine=2, seed=0, max_n1=None, covered=False,
-                 model="homography"):
-    """rr_verify_pairs (model "homography") / rr_verify_pairs_epipolar ("fundamental"): kp1 [rows1, 2],
+                 model="homography", K1=None, K2=None):
+    """rr_verify_pairs (model "homography") / rr_verify_pairs_epipolar ("fundamental") /
+    rr_verify_pairs_essential ("essential", with the intrinsics K1, K2 float64 [P, 3, 3]): kp1 [rows1, 2],
     kp2 [rows2, 2] float32 pixel keypoints, device int64 offsets [P + 1], match int64 [rows1]
-    (rr_match_pairs' output) -> (inliers int32 [P], H or F float64 [P, 3, 3], mask uint8 [rows1]).
+    (rr_match_pairs' output) -> (inliers int32 [P], H, F or E float64 [P, 3, 3], mask uint8 [rows1]).
     covered=True: the pairs cover every side-1 row (the mask is not pre-filled with 0).  No synchronisation."""
     ws_bytes, entry = VERIFY_MODELS[model]
-    E.require_gpu(kp1, off1, kp2, off2, match)
+    calibrated = model == "essential"
+    if calibrated != (K1 is not None and K2 is not None) or (K1 is None) != (K2 is None):
+        raise RuntimeError("verify: K1 and K2 go with model 'essential' and with no other model")
+    E.require_gpu(kp1, off1, kp2, off2, match, K1, K2)
     rows1, rows2, npairs, max_n1 = _pair_args("verify", kp1, off1, kp2, off2, match, max_n1)
     dev = kp1.device
+    mats = ()   # the intrinsics go between max_n1 and th in the calibrated entry
+    if calibrated:
+        for m, what in ((K1, "K1"), (K2, "K2")):
+            if m.dtype != torch.float64 or tuple(m.shape) != (npairs, 3, 3) or not m.is_contiguous():
+                raise RuntimeError("verify: %s must be contiguous float64 [P, 3, 3], got %s %s" % (what, m.dtype, tuple(m.shape)))
+        mats = (E.ptr(K1), E.ptr(K2))
     inliers = torch.empty(npairs, dtype=torch.int32, device=dev)   # written for every pair
     H = torch.empty((npairs, 3, 3), dtype=torch.float64, device=dev)
     mask = (torch.empty if covered and npairs else torch.zeros)(rows1, dtype=torch.uint8, device=dev)
     ws = _workspace(getattr(E.lib(), ws_bytes)(rows1, npairs, int(iters)), dev)
     E.check(getattr(E.lib(), entry)(E.ptr(kp1), E.ptr(off1), rows1, E.ptr(kp2), E.ptr(off2), rows2, E.ptr(match),
-                                    npairs, max_n1, float(th), int(iters), int(refine),
+                                    npairs, max_n1, *mats, float(th), int(iters), int(refine),
                                     int(seed) & 0xFFFFFFFFFFFFFFFF, E.ptr(inliers), E.ptr(H), E.ptr(mask), E.ptr(ws),
                                     ws.numel(), _st()), entry)
     return inliers, H, mask
@@ -782,6 +793,21 @@ def fundamental_dlt(pts1, pts2, weights, off):
     """rr_fundamental_dlt: the arguments of homography_dlt -> F float64 [P, 3, 3] (find_fundamental
     per point set; zeros for a set of fewer than 8 points).  No synchronisation."""
     return _fit_batch("rr_fundamental_dlt", "fundamental", pts1, pts2, weights, off)
+
+
+def essential_5pt(x1, x2):
+    """rr_essential_5pt: x1, x2 float64 [n, 5, 2] normalised points -> (E float64 [n, 10, 3, 3] in ascending
+    root order, zeros past nroots; nroots int32 [n]).  No synchronisation."""
+    E.require_gpu(x1, x2)
+    if x1.dim() != 3 or tuple(x1.shape[1:]) != (5, 2) or x1.shape != x2.shape:
+        raise RuntimeError("five-point: points must be [n, 5, 2] on both sides, got %s and %s" % (tuple(x1.shape), tuple(x2.shape)))
+    if x1.dtype != torch.float64 or x2.dtype != torch.float64 or not x1.is_contiguous() or not x2.is_contiguous():
+        raise RuntimeError("five-point: points must be contiguous float64")
+    n = x1.shape[0]
+    Em = torch.empty((n, 10, 3, 3), dtype=torch.float64, device=x1.device)
+    nroots = torch.empty(n, dtype=torch.int32, device=x1.device)
+    E.check(E.lib().rr_essential_5pt(E.ptr(x1), E.ptr(x2), n, E.ptr(Em), E.ptr(nroots), _st()), "rr_essential_5pt")
+    return Em, nroots
 
 
 EPI_KINDS = {"sampson": E.RR_EPI_SAMPSON, "symmetrical": E.RR_EPI_SYMMETRICAL}

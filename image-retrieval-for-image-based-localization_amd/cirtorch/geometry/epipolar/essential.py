@@ -98,3 +98,19 @@ def relative_camera_motion(R1, t1, R2, t2):
                              % (tuple(R.shape), tuple(t.shape)))
     R = R2 @ R1.transpose(-2, -1)
     return R, t2 - R @ t1
+
+
+def run_5point(points1, points2):
+    """The essential matrices through five correspondences (rr_essential_5pt): points1, points2
+    [B, 5, 2] in normalised coordinates (``K^-1 [x, y, 1]``) -> (E [B, 10, 3, 3] with
+    ``[x2, y2, 1] E [x1, y1, 1]^T = 0``, each of unit Frobenius norm, in ascending root order and zero
+    past the sample's number of solutions; nroots int32 [B], an even number up to 10).  Computed in
+    float64, one GPU thread per sample; GPU tensors only."""
+    if points1.dim() != 3 or tuple(points1.shape[1:]) != (5, 2) or points1.shape != points2.shape:
+        raise ValueError("run_5point: points must be [B, 5, 2] on both sides, got %s and %s"
+                         % (tuple(points1.shape), tuple(points2.shape)))
+    if points1.dtype not in (torch.float32, torch.float64) or points2.dtype != points1.dtype:
+        raise ValueError("run_5point: float32 or float64 on both sides, got %s and %s" % (points1.dtype, points2.dtype))
+    _ops.E.require_gpu(points1, points2)
+    Em, nroots = _ops.essential_5pt(points1.double().contiguous(), points2.double().contiguous())
+    return Em.to(points1.dtype), nroots

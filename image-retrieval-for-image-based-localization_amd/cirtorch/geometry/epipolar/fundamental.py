@@ -67,3 +67,15 @@ def compute_correspond_epilines(points, F_mat):
     nu = a * a + b * b
     nu = torch.where(nu > 0., 1. / torch.sqrt(nu), torch.ones_like(nu))
     return torch.cat([a * nu, b * nu, c * nu], dim=1).permute(0, 2, 1)
+
+
+def fundamental_from_essential(E_mat, K1, K2):
+    """F = K2^-T E K1^-1 (Hartley / Zisserman 9.12, the inverse of ``essential_from_fundamental``): all
+    [..., 3, 3] with the same number of dimensions.  It takes the E of
+    ``verify_pairs(model="essential")`` to the F that ``recover_pose`` expects."""
+    for x, what in ((E_mat, "E_mat"), (K1, "K1"), (K2, "K2")):
+        if x.dim() < 2 or tuple(x.shape[-2:]) != (3, 3):
+            raise ValueError("fundamental_from_essential: %s must be [..., 3, 3], got %s" % (what, tuple(x.shape)))
+    if not E_mat.dim() == K1.dim() == K2.dim():
+        raise ValueError("fundamental_from_essential: E_mat, K1 and K2 must have the same number of dimensions")
+    return torch.linalg.inv(K2).transpose(-2, -1) @ E_mat @ torch.linalg.inv(K1)

@@ -651,7 +651,7 @@ def match_pairs(desc1, desc2, mode="mnn", th=0.8, offsets1=None, offsets2=None, 
 
 
 def verify_pairs(kpts1, kpts2, match, th=3.0, iters=1024, refine=2, seed=0, offsets1=None, offsets2=None, max_n1=None,
-                 model="homography"):
+                 model="homography", K1=None, K2=None):
     """Spatial verification of matched pairs in one call (rr_verify_pairs): per pair a RANSAC
     homography over the kept matches (``match[i] >= 0``), refitted `refine` times by the
     reference's DLT on its inliers -- what ``compute_H_estimation`` (HPatchesEval.py:45-69) gets
@@ -675,9 +675,23 @@ def verify_pairs(kpts1, kpts2, match, th=3.0, iters=1024, refine=2, seed=0, offs
     reference's 8-point ``find_fundamental`` on its inliers, inliers = the matches whose Sampson
     distance is at most `th` pixels.  Same forms and outputs, with F [P, 3, 3] (unit Frobenius
     norm, ``x2^T F x1 = 0``) in place of H; fewer than 7 matches give 0.  On a planar scene or
-    under pure rotation F is not determined and the count is inflated: use the homography there."""
+    under pure rotation F is not determined and the count is inflated: use the homography there, or,
+    with known cameras, the essential matrix.
+
+    model="essential" (rr_verify_pairs_essential) is the calibrated verifier: K1 / K2 [3, 3] (one camera
+    for every pair) or [P, 3, 3] are the intrinsics of the two views, the hypotheses come from a
+    five-point solver on five matches, the refit is the 8-point fit projected onto the essential
+    matrices.  inliers and mask mean what they mean for "fundamental" (Sampson distance in pixels of
+    F = K2^-T E K1^-1); E [P, 3, 3] has unit Frobenius norm and singular values (s, s, 0).  It stays
+    determined on a plane, up to the two motions a plane admits.  Fewer than 5 matches, or a K that
+    cannot be inverted, give 0.  ``fundamental_from_essential(E, K1, K2)`` is what ``recover_pose``
+    takes."""
     if model not in _ops.VERIFY_MODELS:
-        raise ValueError("verify_pairs: model is 'homography' or 'fundamental', got %r" % (model,))
+        raise ValueError("verify_pairs: model is 'homography', 'fundamental' or 'essential', got %r" % (model,))
+    if model == "essential" and (K1 is None or K2 is None):
+        raise ValueError("verify_pairs: model 'essential' needs the intrinsics K1 and K2")
+    if model != "essential" and (K1 is not None or K2 is not None):
+        raise ValueError("verify_pairs: K1 / K2 go with model 'essential', not with %r" % (model,))
     if (offsets1 is None) != (offsets2 is None):
         raise ValueError("verify_pairs: give both offsets1 and offsets2 (ragged) or neither (dense)")
     if kpts1.shape[-1] != 2 or kpts2.shape[-1] != 2:
@@ -689,10 +703,11 @@ def verify_pairs(kpts1, kpts2, match, th=3.0, iters=1024, refine=2, seed=0, offs
     if offsets1 is not None:
         if kpts1.dim() != 2 or kpts2.dim() != 2 or match.dim() != 1 or match.shape[0] != kpts1.shape[0]:
             raise ValueError("verify_pairs: the ragged form takes [rows, 2] keypoints and match [rows1]")
-        _ops.E.require_gpu(kpts1, kpts2, match, offsets1, offsets2)
+        mats = _verify_mats(K1, K2, offsets1.numel() - 1)
+        _ops.E.require_gpu(kpts1, kpts2, match, offsets1, offsets2, K1, K2)
         inl, H, mask = _ops.verify_pairs(kpts1.float().contiguous(), offsets1.contiguous(), kpts2.float().contiguous(),
                                          offsets2.contiguous(), match.contiguous(), th, iters, refine, seed, max_n1,
-                                         model=model)
+                                         model=model, **mats)
         return inl, H, mask.view(torch.bool)
     if kpts1.dim() != kpts2.dim() or kpts1.dim() not in (2, 3) or (kpts1.dim() == 3 and kpts1.shape[0] != kpts2.shape[0]) \
             or tuple(match.shape) != tuple(kpts1.shape[:-1]):
@@ -702,22 +717,30 @@ def verify_pairs(kpts1, kpts2, match, th=3.0, iters=1024, refine=2, seed=0, offs
     n1, n2 = kpts1.shape[-2], kpts2.shape[-2]
     if max_n1 is not None and int(max_n1) < n1:
         raise ValueError("verify_pairs: max_n1 = %d below the pairs' length %d" % (int(max_n1), n1))
-    _ops.E.require_gpu(kpts1, kpts2, match)
+    mats = _verify_mats(K1, K2, p)
+    _ops.E.require_gpu(kpts1, kpts2, match, K1, K2)
     steps = torch.arange(p + 1, dtype=torch.int64, device=kpts1.device)
     inl, H, mask = _ops.verify_pairs(kpts1.float().reshape(p * n1, 2).contiguous(), steps * n1,
                                      kpts2.float().reshape(p * n2, 2).contiguous(), steps * n2,
                                      match.reshape(p * n1).contiguous(), th, iters, refine, seed, n1, covered=True,
-                                     model=model)
+                                     model=model, **mats)
     return inl, H, mask.view(torch.bool).view(match.shape)
 
 
-def _pose_mats(m, p, what):
+def _pose_mats(m, p, what, who="recover_pose"):
     """[3, 3] (one for every pair) or [P, 3, 3] -> contiguous float64 [P, 3, 3]"""
     if tuple(m.shape) == (3, 3):
         m = m.unsqueeze(0).expand(p, 3, 3)
     if tuple(m.shape) != (p, 3, 3):
-        raise ValueError("recover_pose: %s must be [3, 3] or [P, 3, 3] with P = %d, got %s" % (what, p, tuple(m.shape)))
+        raise ValueError("%s: %s must be [3, 3] or [P, 3, 3] with P = %d, got %s" % (who, what, p, tuple(m.shape)))
     return m.double().contiguous()
+
+
+def _verify_mats(K1, K2, p):
+    """the intrinsics of verify_pairs(model="essential") as keyword arguments of _ops.verify_pairs"""
+    if K1 is None:
+        return {}
+    return dict(K1=_pose_mats(K1, p, "K1", "verify_pairs"), K2=_pose_mats(K2, p, "K2", "verify_pairs"))
 
 
 def recover_pose(kpts1, kpts2, match, F, K1, K2, mask=None, offsets1=None, offsets2=None, max_n1=None):

@@ -26,6 +26,12 @@
 //                     Frobenius norm, largest entry positive) and the side-1 mask.
 //   k_fit_batch<F>    rr_fundamental_dlt: the same 8-point routine on caller-supplied points.
 //   k_epi_distance    rr_epipolar_distance.
+//   k_ransac<E>, k_refit<E>   the same two kernels for struct Essential (rr_verify_pairs_essential): the
+//                     pair's intrinsics are its context (K, K^-1 of both views, loaded once per pair),
+//                     a hypothesis is a five-point sample solved by rr_fivepoint.h (up to ten roots,
+//                     scored in one walk as F = K2^-T E K1^-1 with the residual routine below), the
+//                     refit is the 8-point fit projected onto the essential matrices.
+//   k_essential_5pt   rr_essential_5pt: the five-point solver alone, a thread per sample.
 //
 // One residual routine (epi_terms) serves the RANSAC scorer, the refit, the mask and
 // rr_epipolar_distance.  The 8-point routine (fit_block<Fundamental>) is block-wide like the DLT: three
@@ -35,6 +41,7 @@
 //
 // A result depends on nothing but the pair's own data, seed, p and t (block size 256 everywhere).
 #include "rr_ransac.h"
+#include "rr_fivepoint.h"
 
 namespace rr {
 
@@ -244,7 +251,10 @@ struct Fundamental {
     static constexpr bool TRUST_ROOT = true;   // the refit does not count the roots again: the key's root was scored from the same records
     static constexpr int REFIT_OCC = 1;   // no bound: the refit holds 244 VGPRs, the batch fit 193
 
-    static __device__ __forceinline__ int hypotheses(const double (&q)[7][4], double (&F)[3][9]) { return f_from7(q, F); }
+    struct Ctx {};   // a pair is its records
+    static __device__ __forceinline__ Ctx load(const double*, const double*, int) { return {}; }
+
+    static __device__ __forceinline__ int hypotheses(const Ctx&, const double (&q)[7][4], double (&F)[3][9]) { return f_from7(q, F); }
     static __device__ __forceinline__ bool inlier(const double (&f)[9], double x1, double y1, double x2, double y2, double th2) {
         return is_inlier_f(f, x1, y1, x2, y2, th2);
     }
@@ -285,7 +295,7 @@ struct Fundamental {
     }
 
     // rank 2, F = T2^T (f T1), then normalize_transformation
-    static __device__ __forceinline__ void finish(double (&e9)[9], const FitNorm& n, double (&f)[9]) {
+    static __device__ __forceinline__ void finish(const Ctx&, double (&e9)[9], const FitNorm& n, double (&f)[9]) {
         rank2(e9);
         double g[9], o[9];
 #pragma unroll
@@ -307,7 +317,7 @@ struct Fundamental {
     }
 
     // unit Frobenius norm, the entry of largest magnitude (the lowest index among equals) positive
-    static __device__ __forceinline__ void emit(bool have, const double (&f)[9], double* __restrict__ out) {
+    static __device__ __forceinline__ void emit(const Ctx&, bool have, const double (&f)[9], double* __restrict__ out) {
         double ss = 0.0, big = 0.0, sign = 1.0;
 #pragma unroll
         for (int i = 0; i < 9; ++i) {
@@ -319,6 +329,188 @@ struct Fundamental {
         for (int i = 0; i < 9; ++i) out[i] = have ? f[i] / nrm : 0.0;
     }
 };
+
+// ---------------------------------------------------------------- the calibrated model
+// o = a^T b, o = a b (3 x 3 row-major)
+__device__ __forceinline__ void mat3_atb(const double (&a)[9], const double (&b)[9], double (&o)[9]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) o[3 * i + j] = fma(a[i], b[j], fma(a[3 + i], b[3 + j], a[6 + i] * b[6 + j]));
+}
+__device__ __forceinline__ void mat3_ab(const double (&a)[9], const double (&b)[9], double (&o)[9]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) o[3 * i + j] = fma(a[3 * i], b[j], fma(a[3 * i + 1], b[3 + j], a[3 * i + 2] * b[6 + j]));
+}
+
+// inverse by the adjugate -> det
+__device__ __forceinline__ double inv3(const double (&a)[9], double (&o)[9]) {
+    double c[9];
+    c[0] = a[4] * a[8] - a[5] * a[7]; c[1] = a[2] * a[7] - a[1] * a[8]; c[2] = a[1] * a[5] - a[2] * a[4];
+    c[3] = a[5] * a[6] - a[3] * a[8]; c[4] = a[0] * a[8] - a[2] * a[6]; c[5] = a[2] * a[3] - a[0] * a[5];
+    c[6] = a[3] * a[7] - a[4] * a[6]; c[7] = a[1] * a[6] - a[0] * a[7]; c[8] = a[0] * a[4] - a[1] * a[3];
+    const double det = a[0] * c[0] + a[1] * c[3] + a[2] * c[6];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) o[i] = c[i] / det;
+    return det;
+}
+
+// e <- the nearest essential matrix: singular values (s, s, 0), s = (s1 + s2) / 2.  The eigenvectors
+// v of e^T e by the 3 x 3 cyclic Jacobi of rank2; the one of the smallest eigenvalue (ties: the
+// lower index) is dropped, the other two give e <- s (e va) va^T / sa + s (e vb) vb^T / sb.
+__device__ __forceinline__ void essential_project(double (&e)[9]) {
+    double g[9], v[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            g[3 * i + j] = fma(e[i], e[j], fma(e[3 + i], e[3 + j], e[6 + i] * e[6 + j]));
+            v[3 * i + j] = i == j ? 1.0 : 0.0;
+        }
+#pragma unroll 1
+    for (int sweep = 0; sweep < V_SWEEPS; ++sweep) {
+        const bool r0 = rot3<0, 1>(g, v);
+        const bool r1 = rot3<0, 2>(g, v);
+        const bool r2 = rot3<1, 2>(g, v);
+        if (!(r0 || r1 || r2)) break;
+    }
+    const bool m1 = g[4] < g[0];
+    const bool m2 = g[8] < (m1 ? g[4] : g[0]);
+    const bool drop0 = !m2 && !m1;   // the smallest eigenvalue is number 0 / number 2 (otherwise number 1)
+    const bool drop2 = m2;
+    double va[3], vb[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        va[k] = drop0 ? v[3 * k + 1] : v[3 * k];
+        vb[k] = drop2 ? v[3 * k + 1] : v[3 * k + 2];
+    }
+    const double sa = sqrt(drop0 ? g[4] : g[0]), sb = sqrt(drop2 ? g[4] : g[8]);
+    const double s = 0.5 * (sa + sb), fa = s / sa, fb = s / sb;
+    double o[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double wa = fa * fma(e[3 * i], va[0], fma(e[3 * i + 1], va[1], e[3 * i + 2] * va[2]));
+        const double wb = fb * fma(e[3 * i], vb[0], fma(e[3 * i + 1], vb[1], e[3 * i + 2] * vb[2]));
+#pragma unroll
+        for (int j = 0; j < 3; ++j) o[3 * i + j] = fma(wa, va[j], wb * vb[j]);
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) e[i] = o[i];
+}
+
+// The essential matrix as a model of the skeleton: its matrices are fundamental matrices in
+// pixels, F = K2^-T E K1^-1, so the records, the score, the refit's acceptance and the mask are
+// Fundamental's; only the family of matrices differs.  rr.h states every rule.
+struct Essential {
+    // a key holds 16 t + root; the ten roots of a sample are scored in ONE walk over a generic pointer
+    static constexpr int SAMPLE = 5, FIT_MIN = 8, ROOTS = FP_ROOTS, KEY_SLOTS = 16, ACC = 36, WALK_UNROLL = 1;
+    static constexpr bool WALK_SPLIT = false;
+    static constexpr bool TRUST_ROOT = true;
+    static constexpr int REFIT_OCC = 1;
+
+    struct Ctx {   // the intrinsics of the pair and their inverses
+        double k1[9], k2[9], i1[9], i2[9];
+        bool ok;   // every entry finite, |det| positive and finite on both sides
+    };
+    static __device__ __forceinline__ Ctx load(const double* __restrict__ K1, const double* __restrict__ K2, int p) {
+        Ctx c;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            c.k1[i] = K1[9 * (long long)p + i];
+            c.k2[i] = K2[9 * (long long)p + i];
+        }
+        const double d1 = inv3(c.k1, c.i1), d2 = inv3(c.k2, c.i2);
+        c.ok = all_finite9(c.k1) && all_finite9(c.k2) && isfinite(d1) && isfinite(d2) && fabs(d1) > 0.0 && fabs(d2) > 0.0 &&
+               all_finite9(c.i1) && all_finite9(c.i2);
+        return c;
+    }
+
+    // the five-point solver on K^-1 (x, y, 1)^T, every root as F = K2^-T E K1^-1
+    static __device__ __forceinline__ int hypotheses(const Ctx& c, const double (&q)[5][4], double (&F)[FP_ROOTS][9]) {
+        double h1[5][3], h2[5][3];
+#pragma unroll
+        for (int j = 0; j < 5; ++j)
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                h1[j][r] = fma(c.i1[3 * r], q[j][0], fma(c.i1[3 * r + 1], q[j][1], c.i1[3 * r + 2]));
+                h2[j][r] = fma(c.i2[3 * r], q[j][2], fma(c.i2[3 * r + 1], q[j][3], c.i2[3 * r + 2]));
+            }
+        const int n = c.ok ? five_point(h1, h2, F) : 0;
+#pragma unroll
+        for (int k = 0; k < FP_ROOTS; ++k) {
+            double t[9], f[9];
+            mat3_ab(F[k], c.i1, t);
+            mat3_atb(c.i2, t, f);
+            const bool ok = k < n && all_finite9(f);
+#pragma unroll
+            for (int i = 0; i < 9; ++i) F[k][i] = ok ? f[i] : 0.0;
+        }
+        return n;
+    }
+    static __device__ __forceinline__ bool inlier(const double (&f)[9], double x1, double y1, double x2, double y2, double th2) {
+        return is_inlier_f(f, x1, y1, x2, y2, th2);
+    }
+    static __device__ __forceinline__ void accumulate(const FitNorm& n, double x1, double y1, double x2, double y2, double w,
+                                                      double (&acc)[36]) {
+        Fundamental::accumulate(n, x1, y1, x2, y2, w, acc);
+    }
+    static __device__ __forceinline__ void write_matrix(const double (&acc)[36], double* a) { Fundamental::write_matrix(acc, a); }
+
+    // E <- K2^T F K1, projected
+    static __device__ __forceinline__ void to_essential(const Ctx& c, const double (&f)[9], double (&e)[9]) {
+        double t[9];
+        mat3_ab(f, c.k1, t);
+        mat3_atb(c.k2, t, e);
+        essential_project(e);
+    }
+
+    // find_fundamental, E' = K2^T F' K1 projected onto the essential matrices, back to pixels
+    static __device__ __forceinline__ void finish(const Ctx& c, double (&e9)[9], const FitNorm& n, double (&f)[9]) {
+        double f1[9], e[9], t[9];
+        Fundamental::finish({}, e9, n, f1);
+        to_essential(c, f1, e);
+        mat3_ab(e, c.i1, t);
+        mat3_atb(c.i2, t, f);
+    }
+
+    // E = K2^T F K1 projected, then Fundamental's rule
+    static __device__ __forceinline__ void emit(const Ctx& c, bool have, const double (&f)[9], double* __restrict__ out) {
+        double e[9];
+        to_essential(c, f, e);
+        Fundamental::emit({}, have && all_finite9(e), e, out);
+    }
+};
+
+// rr_essential_5pt: one thread per sample
+__global__ void __launch_bounds__(V_TB) k_essential_5pt(const double* __restrict__ x1, const double* __restrict__ x2, int n,
+                                                        double* __restrict__ Eout, int* __restrict__ nroots) {
+    for (long long s = (long long)blockIdx.x * V_TB + threadIdx.x; s < n; s += (long long)gridDim.x * V_TB) {
+        double h1[5][3], h2[5][3];
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+            const double2 a = *reinterpret_cast<const double2*>(x1 + 10 * s + 2 * j);
+            const double2 b = *reinterpret_cast<const double2*>(x2 + 10 * s + 2 * j);
+            h1[j][0] = a.x; h1[j][1] = a.y; h1[j][2] = 1.0;
+            h2[j][0] = b.x; h2[j][1] = b.y; h2[j][2] = 1.0;
+        }
+        double E[FP_ROOTS][9];
+        const int nr = five_point(h1, h2, E);
+        int good = 0;
+#pragma unroll
+        for (int k = 0; k < FP_ROOTS; ++k) {
+            const bool ok = k < nr && all_finite9(E[k]);
+            good += ok ? 1 : 0;
+            Fundamental::emit({}, ok, E[k], Eout + 90 * s + 9 * k);
+        }
+        nroots[s] = good == nr ? nr : 0;   // a root that is not finite: the sample is refused whole
+        if (good != nr) {
+#pragma unroll 1
+            for (int i = 0; i < 90; ++i) Eout[90 * s + i] = 0.0;
+        }
+    }
+}
 
 __global__ void __launch_bounds__(V_TB) k_epi_distance(const double* __restrict__ p1, const double* __restrict__ p2,
                                                        const double* __restrict__ Fm, const long long* __restrict__ off,
@@ -359,7 +551,34 @@ int rr_verify_pairs_epipolar(const float* kp1, const long long* off1, long long 
                              double th, int iters, int refine, unsigned long long seed, int* inliers, double* F,
                              unsigned char* mask, void* workspace, size_t workspace_bytes, void* stream) {
     return verify_pairs_impl<Fundamental>("rr_verify_pairs_epipolar", kp1, off1, rows1, kp2, off2, rows2, match, npairs, max_n1,
-                                          th, iters, refine, seed, inliers, F, mask, workspace, workspace_bytes, stream);
+                                          th, iters, refine, seed, nullptr, nullptr, inliers, F, mask, workspace,
+                                          workspace_bytes, stream);
+}
+
+size_t rr_verify_essential_workspace_bytes(long long rows1, int npairs, int iters) {
+    return measured(layout, rows1, npairs, iters);
+}
+
+int rr_verify_pairs_essential(const float* kp1, const long long* off1, long long rows1, const float* kp2,
+                              const long long* off2, long long rows2, const long long* match, int npairs, int max_n1,
+                              const double* K1, const double* K2, double th, int iters, int refine, unsigned long long seed,
+                              int* inliers, double* E, unsigned char* mask, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+    return verify_pairs_impl<Essential>("rr_verify_pairs_essential", kp1, off1, rows1, kp2, off2, rows2, match, npairs, max_n1,
+                                        th, iters, refine, seed, K1, K2, inliers, E, mask, workspace, workspace_bytes, stream);
+}
+
+int rr_essential_5pt(const double* x1, const double* x2, int n, double* E, int* nroots, void* stream) {
+    const std::string w("rr_essential_5pt");
+    if (n < 0) return fail(RR_EINVAL, w + ": negative size");
+    if (n > 0 && (!x1 || !x2)) return fail(RR_EINVAL, w + ": null points");
+    if (n > 0 && (!E || !nroots)) return fail(RR_EINVAL, w + ": null output");
+    if ((((uintptr_t)x1) & 15) || (((uintptr_t)x2) & 15)) return fail(RR_EINVAL, w + ": points must be 16-byte aligned");
+    if (n == 0) return RR_OK;
+    const int blocks = (n + V_TB - 1) / V_TB;
+    hipLaunchKernelGGL(k_essential_5pt, dim3((unsigned)(blocks < 65535 ? blocks : 65535)), dim3(V_TB), 0, as_stream(stream), x1,
+                       x2, n, E, nroots);
+    return check_launch("rr_essential_5pt");
 }
 
 int rr_fundamental_dlt(const double* pts1, const double* pts2, const double* weights, const long long* off,

@@ -1,5 +1,5 @@
-// librr.so — what the two geometric verifiers (rr_verify.hip: homography, rr_epipolar.hip:
-// fundamental matrix) and the pose entry after them (rr_pose.hip) share: the pair ranges, the
+// librr.so — what the geometric verifiers (rr_verify.hip: homography, rr_epipolar.hip:
+// fundamental and essential matrix) and the pose entry after them (rr_pose.hip) share: the pair ranges, the
 // counter-hash sampler of rr.h, the compaction of kept matches into records, the block reductions
 // with one fixed order, the round-robin cyclic Jacobi on a symmetric 9 x 9 matrix in LDS, the
 // cyclic Jacobi on a symmetric 3 x 3 in registers, the workspace layout, and on top of them the
@@ -11,6 +11,7 @@
 #include "rr_workspace.h"
 
 #include <math.h>
+#include <type_traits>
 
 namespace rr {
 
@@ -313,18 +314,20 @@ inline VerifyWs layout(Arena& a, long long rows1, int npairs, int iters) {
 
 // ================================================================ the RANSAC skeleton
 // Everything above the primitives, once, for a model M: a struct of constants and
-// __device__ __forceinline__ static functions (Homography: rr_verify.hip, Fundamental: rr_epipolar.hip).
+// __device__ __forceinline__ static functions (Homography: rr_verify.hip, Fundamental and Essential: rr_epipolar.hip).
 //   SAMPLE      records of a minimal sample          FIT_MIN     fewest points of the least-squares fit
 //   ROOTS       most matrices through one sample     KEY_SLOTS   key values per hypothesis (>= ROOTS)
 //   ACC         sums the fit's normal matrix is of   REFIT_OCC   blocks per CU k_refit / k_fit_batch are built for
 //   WALK_UNROLL unroll factor of the scoring walk    WALK_SPLIT  the walk is written once per address space
 //   TRUST_ROOT  the refit takes matrix `root` of the winner's sample as it comes (false: only where hypotheses() > 0)
-//   hypotheses(q, Mx) -> n      the matrices through the sample q; those past n are all zero
+//   Ctx, load(K1, K2, p)        what the model knows of pair p besides its records (empty, or the intrinsics);
+//                               it reaches hypotheses, finish and emit
+//   hypotheses(ctx, q, Mx) -> n the matrices through the sample q; those past n are all zero
 //   inlier(m, x1, y1, x2, y2, th2)
 //   accumulate(n, x1, y1, x2, y2, w, acc)   one point, normalised by n, into the ACC sums
 //   write_matrix(acc, a)        the block's totals -> the symmetric 9 x 9 matrix in LDS
-//   finish(e9, n, out)          its smallest eigenvector -> the de-normalised 3 x 3
-//   emit(have, m, out)          the refit's final write
+//   finish(ctx, e9, n, out)     its smallest eigenvector -> the de-normalised 3 x 3
+//   emit(ctx, have, m, out)     the refit's final write
 // A model adds no kernel and no host code: its two entry points are verify_pairs_impl<M> and
 // fit_batch_impl<M>.  The arithmetic of a model stays in its own file, statement for statement: the
 // files are compiled with the default floating-point contraction, so moving an expression moves bits.
@@ -355,6 +358,7 @@ template <typename M>
 __global__ void __launch_bounds__(V_TB) k_ransac(const double* __restrict__ rec, const long long* __restrict__ off1,
                                                  long long rows1, const int* __restrict__ cnt, int npairs, int iters,
                                                  int chunks, double th2, unsigned long long seed,
+                                                 const double* __restrict__ K1, const double* __restrict__ K2,
                                                  unsigned long long* __restrict__ best) {
     __shared__ __attribute__((aligned(16))) double s_rec[V_STAGE * 4];
     __shared__ unsigned long long s_red[4];
@@ -379,7 +383,10 @@ __global__ void __launch_bounds__(V_TB) k_ransac(const double* __restrict__ rec,
                 double q[M::SAMPLE][4];
                 sample<M::SAMPLE>(src, seed, p, t, m, q);
                 double Mx[M::ROOTS][9];
-                if (M::hypotheses(q, Mx) > 0) {
+                // once per pair and thread, next to its only use: loaded before the staging it stays live across
+                // it and k_ransac<Essential> spills 236 B per lane more
+                const typename M::Ctx ctx = M::load(K1, K2, p);
+                if (M::hypotheses(ctx, q, Mx) > 0) {
                     int c[M::ROOTS];
                     if constexpr (M::WALK_SPLIT) {   // a walk per address space: LDS reads, global reads
                         if (staged) count_all<M>(Mx, s_rec, m, th2, c);
@@ -444,7 +451,7 @@ struct FitNorm {
 // points (out untouched).  Three passes, each a per-thread chain over i = tid, tid + 256, ... and a
 // block sum: the means; the mean distances; the M::ACC sums of the normal matrix.
 template <typename M, typename Src>
-__device__ __forceinline__ bool fit_block(const Src& src, FitLds<M>& L, double (&out)[9]) {
+__device__ __forceinline__ bool fit_block(const typename M::Ctx& ctx, const Src& src, FitLds<M>& L, double (&out)[9]) {
     const int tid = threadIdx.x;
     double x1, y1, x2, y2, w;
     // normalize_points: mean, then sqrt(2) / (mean distance to it + eps)
@@ -477,7 +484,7 @@ __device__ __forceinline__ bool fit_block(const Src& src, FitLds<M>& L, double (
     // the eigenvector of the smallest eigenvalue (ties: the lower index)
     double e9[9];
     jacobi_smallest9(L.a, L.v, e9);
-    M::finish(e9, nrm, out);
+    M::finish(ctx, e9, nrm, out);
     return true;
 }
 
@@ -489,8 +496,8 @@ __global__ void __launch_bounds__(V_TB, M::REFIT_OCC)
 k_refit(const float* __restrict__ kp1, const long long* __restrict__ off1, long long rows1, const float* __restrict__ kp2,
         const long long* __restrict__ off2, long long rows2, const long long* __restrict__ match, int npairs, int max_n1,
         const double* __restrict__ rec, const int* __restrict__ cnt, const unsigned long long* __restrict__ best, int chunks,
-        double th2, int refine, unsigned long long seed, int* __restrict__ inliers, double* __restrict__ Mout,
-        unsigned char* __restrict__ mask) {
+        double th2, int refine, unsigned long long seed, const double* __restrict__ K1, const double* __restrict__ K2,
+        int* __restrict__ inliers, double* __restrict__ Mout, unsigned char* __restrict__ mask) {
     __shared__ FitLds<M> L;
     __shared__ unsigned long long s_red[4];
     __shared__ int s_cnt[4];
@@ -502,6 +509,7 @@ k_refit(const float* __restrict__ kp1, const long long* __restrict__ off1, long 
         if (n1 > max_n1) n1 = max_n1;
         const int m = cnt[p];
         const double* r = rec + 4 * b1;
+        const typename M::Ctx ctx = M::load(K1, K2, p);
         unsigned long long key = 0ull;
         for (int c = tid; c < chunks; c += V_TB) {
             const unsigned long long k = best[(long long)p * chunks + c];
@@ -520,7 +528,7 @@ k_refit(const float* __restrict__ kp1, const long long* __restrict__ off1, long 
                 double q[M::SAMPLE][4];
                 sample<M::SAMPLE>(r, seed, p, t, m, q);
                 double Mx[M::ROOTS][9];
-                const int n = M::hypotheses(q, Mx);
+                const int n = M::hypotheses(ctx, q, Mx);
                 have = M::TRUST_ROOT || n > 0;
 #pragma unroll
                 for (int i = 0; i < 9; ++i) {
@@ -537,7 +545,7 @@ k_refit(const float* __restrict__ kp1, const long long* __restrict__ off1, long 
 #pragma unroll
                 for (int i = 0; i < 9; ++i) src.mx[i] = mx[i];
                 double m2[9];
-                if (!fit_block<M>(src, L, m2) || !all_finite9(m2)) break;
+                if (!fit_block<M>(ctx, src, L, m2) || !all_finite9(m2)) break;
                 const int c2 = count_block<M>(m2, r, m, th2, s_cnt);
                 if (c2 < count) break;
                 count = c2;
@@ -552,7 +560,7 @@ k_refit(const float* __restrict__ kp1, const long long* __restrict__ off1, long 
         }
         if (tid == 0) {
             inliers[p] = count;
-            M::emit(have, mx, Mout + 9 * (long long)p);
+            M::emit(ctx, have, mx, Mout + 9 * (long long)p);
         }
         // the mask straight from the rows: the same values and the same test as the records
         for (long long i = tid; i < n1; i += V_TB) {
@@ -584,7 +592,7 @@ k_fit_batch(const double* __restrict__ p1, const double* __restrict__ p2, const 
         double mx[9];
 #pragma unroll
         for (int i = 0; i < 9; ++i) mx[i] = 0.0;
-        fit_block<M>(src, L, mx);
+        fit_block<M>(typename M::Ctx{}, src, L, mx);
         if (threadIdx.x == 0) {
 #pragma unroll
             for (int i = 0; i < 9; ++i) Mout[9 * (long long)p + i] = mx[i];
@@ -594,12 +602,13 @@ k_fit_batch(const double* __restrict__ p1, const double* __restrict__ p2, const 
 }
 
 // ---------------------------------------------------------------- host: launches (argument checks: rr_internal.h)
-// rr_verify_pairs / rr_verify_pairs_epipolar: compaction, k_ransac<M>, k_refit<M>
+// rr_verify_pairs / rr_verify_pairs_epipolar / rr_verify_pairs_essential: compaction, k_ransac<M>, k_refit<M>
+// (K1, K2: the per-pair data of a model with a Ctx, NULL otherwise)
 template <typename M>
 int verify_pairs_impl(const char* name, const float* kp1, const long long* off1, long long rows1, const float* kp2,
                       const long long* off2, long long rows2, const long long* match, int npairs, int max_n1, double th,
-                      int iters, int refine, unsigned long long seed, int* inliers, double* Mout, unsigned char* mask,
-                      void* workspace, size_t workspace_bytes, void* stream) {
+                      int iters, int refine, unsigned long long seed, const double* K1, const double* K2, int* inliers,
+                      double* Mout, unsigned char* mask, void* workspace, size_t workspace_bytes, void* stream) {
     const std::string w(name);
     if (npairs >= 0 && rows1 >= 0 && rows2 >= 0 && max_n1 >= 0) {   // a negative size is reported first, by check_pair_args
         if (iters < 1) return fail(RR_EINVAL, w + ": iters must be >= 1");
@@ -611,6 +620,10 @@ int verify_pairs_impl(const char* name, const float* kp1, const long long* off1,
     if (rc) return rc;
     if (npairs > 0 && (rows1 > 0 && !mask)) return fail(RR_EINVAL, w + ": null output");
     if (npairs > 0 && (!inliers || !Mout)) return fail(RR_EINVAL, w + ": null output");
+    if constexpr (!std::is_empty<typename M::Ctx>::value) {   // a model with per-pair data: the two intrinsics
+        if (npairs > 0 && (!K1 || !K2)) return fail(RR_EINVAL, w + ": null K");
+        if ((((uintptr_t)K1) & 15) || (((uintptr_t)K2) & 15)) return fail(RR_EINVAL, w + ": K must be 16-byte aligned");
+    }
     Arena arena(workspace, workspace_bytes);
     const auto [rec, cnt, best] = layout(arena, rows1, npairs, iters);
     if (!workspace || !arena.fits()) return fail(RR_ENOSPACE, w + ": workspace too small");
@@ -623,11 +636,11 @@ int verify_pairs_impl(const char* name, const float* kp1, const long long* off1,
     rc = check_launch((w + ": compact").c_str());
     if (rc) return rc;
     hipLaunchKernelGGL(k_ransac<M>, dim3((unsigned)chunks, gp), dim3(V_TB), 0, s, rec, off1, rows1, cnt, npairs, iters,
-                       chunks, th * th, seed, best);
+                       chunks, th * th, seed, K1, K2, best);
     rc = check_launch((w + ": ransac").c_str());
     if (rc) return rc;
     hipLaunchKernelGGL(k_refit<M>, dim3(gp), dim3(V_TB), 0, s, kp1, off1, rows1, kp2, off2, rows2, match, npairs, max_n1,
-                       rec, cnt, best, chunks, th * th, refine, seed, inliers, Mout, mask);
+                       rec, cnt, best, chunks, th * th, refine, seed, K1, K2, inliers, Mout, mask);
     return check_launch((w + ": refit").c_str());
 }
 

@@ -120,7 +120,10 @@ struct Homography {
     // 3 blocks per CU (no scratch): while one wave of a block runs its Jacobi rotations the other blocks keep the CU busy
     static constexpr int REFIT_OCC = 3;
 
-    static __device__ __forceinline__ int hypotheses(const double (&q)[4][4], double (&M)[1][9]) { return h_from4(q, M[0]) ? 1 : 0; }
+    struct Ctx {};   // a pair is its records
+    static __device__ __forceinline__ Ctx load(const double*, const double*, int) { return {}; }
+
+    static __device__ __forceinline__ int hypotheses(const Ctx&, const double (&q)[4][4], double (&M)[1][9]) { return h_from4(q, M[0]) ? 1 : 0; }
     static __device__ __forceinline__ bool inlier(const double (&h)[9], double x1, double y1, double x2, double y2, double th2) {
         return is_inlier(h, x1, y1, x2, y2, th2);
     }
@@ -170,7 +173,7 @@ struct Homography {
     }
 
     // H = T2^-1 (h T1) / (H[2][2] + eps)
-    static __device__ __forceinline__ void finish(const double (&e9)[9], const FitNorm& n, double (&h)[9]) {
+    static __device__ __forceinline__ void finish(const Ctx&, const double (&e9)[9], const FitNorm& n, double (&h)[9]) {
         double g[9];
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
@@ -191,7 +194,7 @@ struct Homography {
         for (int i = 0; i < 9; ++i) h[i] = o[i] / den;
     }
 
-    static __device__ __forceinline__ void emit(bool, const double (&h)[9], double* out) {   // h is all zero without a winner
+    static __device__ __forceinline__ void emit(const Ctx&, bool, const double (&h)[9], double* out) {   // h is all zero without a winner
 #pragma unroll
         for (int i = 0; i < 9; ++i) out[i] = h[i];
     }
@@ -212,7 +215,7 @@ int rr_verify_pairs(const float* kp1, const long long* off1, long long rows1, co
                     unsigned long long seed, int* inliers, double* H, unsigned char* mask, void* workspace,
                     size_t workspace_bytes, void* stream) {
     return verify_pairs_impl<Homography>("rr_verify_pairs", kp1, off1, rows1, kp2, off2, rows2, match, npairs, max_n1, th, iters,
-                                         refine, seed, inliers, H, mask, workspace, workspace_bytes, stream);
+                                         refine, seed, nullptr, nullptr, inliers, H, mask, workspace, workspace_bytes, stream);
 }
 
 int rr_homography_dlt(const double* pts1, const double* pts2, const double* weights, const long long* off,

@@ -534,6 +534,82 @@ enum rr_epi_kind { RR_EPI_SAMPSON = 0, RR_EPI_SYMMETRICAL = 1 };
 int rr_epipolar_distance(const double* pts1, const double* pts2, const double* F, const long long* off, long long rows,
                          int npairs, int kind, int squared, double eps, double* out, void* stream);
 
+/* Calibrated verification of matched pairs (rr_epipolar.hip, rr_fivepoint.h): a RANSAC essential
+ * matrix per pair from five-point samples -- the model for two views whose intrinsics are known.
+ * It has five degrees of freedom instead of seven and stays determined (up to two discrete
+ * solutions) on a planar scene.  The arguments of rr_verify_pairs_epipolar plus
+ *   K1, K2 [npairs][3][3]  float64 row-major intrinsics of the two views, DEVICE, 16-byte aligned
+ *   E [npairs][3][3]       float64 row-major, x2n^T E x1n = 0 for xn = K^-1 [x, y, 1]^T
+ * Records, score, the refit's acceptance and the mask are those of rr_verify_pairs_epipolar, in
+ * pixels: a matrix E is scored as F = K2^-T E K1^-1, so inliers and mask mean the same under both
+ * models.  Per pair p:
+ *  a. records: step a of rr_verify_pairs.  K1^-1 and K2^-1 by the adjugate divided by the
+ *     determinant.  A K with an entry that is not finite, a determinant that is zero or not finite,
+ *     or an inverse with an entry that is not finite fails the pair (step e).
+ *  b. hypothesis t in [0, iters): five distinct record indices by the hash and the partial
+ *     Fisher-Yates draw of rr_verify_pairs with j = 0 .. 4.  The five-point solver on the homogeneous
+ *     points h1 = K1^-1 [x1, y1, 1]^T, h2 = K2^-1 [x2, y2, 1]^T (not divided by their last entry):
+ *     1. the 5 x 9 system A with rows h2 (x) h1 (entry 3 a + b = h2_a h1_b).  Five Householder
+ *        reflections H_k = I - 2 v_k v_k^T / v_k^T v_k, k = 0 .. 4, make the 9 x 5 matrix A^T upper
+ *        triangular: v_k = x + sign(x_0) |x| e_0 on entries k .. 8, x the current column k from its
+ *        diagonal down (sign(0) = +).  X, Y, Z, W = H_0 H_1 H_2 H_3 H_4 e_j, j = 5, 6, 7, 8, as 3 x 3
+ *        row-major matrices: an orthonormal basis of the null space, and E = x X + y Y + z Z + W.  (The
+ *        basis whose entries 5 .. 8 are unit vectors was measured first: its entries reach 1e4 on
+ *        normalised points and one sample in thirty loses every digit in step 2.)
+ *     2. det E = 0 (expanded along the first row) and the nine entries of 2 E E^T E - tr(E E^T) E = 0
+ *        in row-major order are ten cubics in (x, y, z): a 10 x 20 matrix in the monomials
+ *          x^3, y^3, x^2 y, x y^2, x^2 z, x^2, y^2 z, y^2, xyz, xy | x z^2, xz, x, y z^2, yz, y, z^3, z^2, z, 1,
+ *        reduced by Gauss-Jordan with partial pivoting on its first ten columns.
+ *     3. with <m> the row whose pivot is the monomial m, the three rows <x^2 z> - z <x^2>,
+ *        <y^2 z> - z <y^2>, <xyz> - z <xy> are x bx(z) + y by(z) + bc(z) with deg bx = deg by = 3,
+ *        deg bc = 4 (Nister).  The determinant of that 3 x 3 matrix, expanded along its first row, is a
+ *        polynomial c(z) of degree 10.  Root rule: c10 == 0 or a coefficient that is not finite gives
+ *        no root.  All roots lie in |z| < Bz = 1 + max_i |c_i / c10|.  For d = 1 .. 10 the real roots
+ *        of derivative number 10 - d of c (degree d) are found from those of derivative number 11 - d:
+ *        these and -Bz, Bz cut the line into intervals in ascending order, and an interval holds a
+ *        root where the sign (value < 0) of the polynomial differs at its ends; the root is the
+ *        midpoint after 48 bisection steps, followed by 3 Newton steps, each kept only where it
+ *        stays inside the last bracket.  Every simple real root is found, in ascending order; two
+ *        roots between which c does not change sign at the computed critical point (a double root,
+ *        or a pair closer than that critical point's error) are not found and count as none.
+ *     4. at a root z the 3 x 3 matrix has the null vector (x, y, 1): the cross product n of two of
+ *        its rows, the pair (0,1), (0,2), (1,2) with the largest |n_2| (the first among equals),
+ *        x = n_0 / n_2, y = n_1 / n_2.  Root number r (ascending z) gives E, and F = K2^-T E K1^-1; a
+ *        root whose F has an entry that is not finite scores 0.  At most 10 roots.
+ *  c. score of a root: step c of rr_verify_pairs_epipolar on F.  The winner is (score desc, t asc,
+ *     root asc).
+ *  d. refit, `refine` times: S = the inliers of F; when |S| >= 8, F' = the unweighted
+ *     rr_fundamental_dlt fit on S in pixels, E' = K2^T F' K1 (essential_from_fundamental,
+ *     essential.py:8-18), E'' = the projection of E' onto the essential matrices: with v_i the
+ *     eigenvectors of E'^T E' by the 3 x 3 cyclic Jacobi of rr_fundamental_dlt, the one of the smallest
+ *     eigenvalue dropped (the lower index among equals), s_i = sqrt(eigenvalue), s = (s_a + s_b) / 2,
+ *     E'' = s (E' v_a) v_a^T / s_a + s (E' v_b) v_b^T / s_b = U diag(s, s, 0) V^T; F'' = K2^-T E'' K1^-1
+ *     replaces F when it is finite and score(F'') >= score(F), otherwise (and when |S| < 8) the refit
+ *     stops.  On a plane the 8-point fit is rank deficient and the rule keeps the minimal solution.
+ *  e. inliers[p] = score(F); mask as rr_verify_pairs_epipolar; E = K2^T F K1 projected as in step d,
+ *     scaled to unit Frobenius norm with its entry of largest magnitude positive (the lowest
+ *     row-major index among equal magnitudes).  M < 5, a failed K or no root with a score above 0:
+ *     inliers 0, E all zeros, mask 0.
+ * On a plane two essential matrices explain the points (the true one and its twisted twin); either
+ * may win.  workspace: rr_verify_essential_workspace_bytes(rows1, npairs, iters).  Nothing waits for
+ * the host (graph-capturable).  Bad arguments are refused as by rr_verify_pairs_epipolar, and so are
+ * a null or misaligned K1 / K2, before anything is enqueued; npairs == 0 returns RR_OK and launches
+ * nothing. */
+size_t rr_verify_essential_workspace_bytes(long long rows1, int npairs, int iters);
+int rr_verify_pairs_essential(const float* kp1, const long long* off1, long long rows1, const float* kp2,
+                              const long long* off2, long long rows2, const long long* match, int npairs, int max_n1,
+                              const double* K1, const double* K2, double th, int iters, int refine, unsigned long long seed,
+                              int* inliers, double* E, unsigned char* mask, void* workspace, size_t workspace_bytes,
+                              void* stream);
+/* The five-point solver of step b above alone, one thread per sample.
+ *   x1, x2 [n][5][2]  float64 normalised points (h = [x, y, 1]), 16-byte aligned
+ *   E [n][10][3][3]   float64: the solutions in ascending root order, each scaled to unit Frobenius
+ *                     norm with its entry of largest magnitude positive; all zeros past nroots[i]
+ *   nroots [n]        int32; a sample with a root whose E is not finite has nroots 0 and zeros
+ * n < 0, null pointers and misaligned points are refused before anything is enqueued; n == 0
+ * returns RR_OK. */
+int rr_essential_5pt(const double* x1, const double* x2, int n, double* E, int* nroots, void* stream);
+
 /* Relative pose of verified pairs (rr_pose.hip): the essential matrix of a fundamental matrix, its
  * four candidate motions, the triangulation of the pair's matches under each and the choice of the
  * motion that puts the most points in front of both cameras.  Brings essential_from_fundamental
