@@ -195,6 +195,20 @@ def pixels_to_unit(x):
     return lut[x.long()]
 
 
+def _stem_norm_arrays(mean, std):
+    """the stem entries' (mean[3], std[3], do_normalize) arguments"""
+    do = mean is not None
+    m = (ctypes.c_float * 3)(*mean) if do else (ctypes.c_float * 3)()
+    s = (ctypes.c_float * 3)(*std) if do else (ctypes.c_float * 3)(1, 1, 1)
+    return m, s, int(do)
+
+
+def _stem_pooled_size(h, w):
+    """(hp, wp) of the stem's output: conv 7x7/s2/p3, then max-pool 3x3/s2/p1"""
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    return (ho - 1) // 2 + 1, (wo - 1) // 2 + 1
+
+
 def stem_conv_pool(img, wpk, scale, shift, leaky=True, slope=0.01, mean=None, std=None):
     """Fused normalise + conv1 7x7/s2/p3 + BN + act + maxpool 3x3/s2/p1
     (cirtorch/backbones/resnet.py:59-66): [N, 3, H, W] float32 -> [N, Hp, Wp, 64] in wpk's dtype
@@ -207,14 +221,11 @@ def stem_conv_pool(img, wpk, scale, shift, leaky=True, slope=0.01, mean=None, st
     n, c, h, w = img.shape
     if c != 3:
         raise RuntimeError("stem_conv_pool: expected 3-channel images, got %d" % c)
-    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-    hp, wp = (ho - 1) // 2 + 1, (wo - 1) // 2 + 1
+    hp, wp = _stem_pooled_size(h, w)
     y = torch.empty((n, hp, wp, 64), dtype=wpk.dtype, device=img.device)
-    do = mean is not None
-    m = (ctypes.c_float * 3)(*mean) if do else (ctypes.c_float * 3)()
-    s = (ctypes.c_float * 3)(*std) if do else (ctypes.c_float * 3)(1, 1, 1)
+    m, s, do = _stem_norm_arrays(mean, std)
     fn = E.lib().rr_stem_conv_pool_u8 if u8 else E.lib().rr_stem_conv_pool
-    E.check(fn(E.ptr(img), n, h, w, m, s, int(do), E.ptr(wpk), E.ptr(scale), E.ptr(shift),
+    E.check(fn(E.ptr(img), n, h, w, m, s, do, E.ptr(wpk), E.ptr(scale), E.ptr(shift),
                E.RR_ACT_LEAKY if leaky else E.RR_ACT_IDENTITY, float(slope), E.ptr(y), hp, wp,
                E.dtype_code(wpk.dtype), _st()), "rr_stem_conv_pool")
     return y
@@ -275,13 +286,10 @@ def stem_conv_pool_ragged(images, h, w, wpk, scale, shift, leaky=True, slope=0.0
     if not u8 and ref.dtype != torch.float32:
         images = [t.float() if t is not None else None for t in images]
     ptrs, ext, kept = _ragged(images)
-    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-    hp, wp = (ho - 1) // 2 + 1, (wo - 1) // 2 + 1
+    hp, wp = _stem_pooled_size(h, w)
     y = torch.empty((len(images), hp, wp, 64), dtype=wpk.dtype, device=ref.device)
-    do = mean is not None
-    m = (ctypes.c_float * 3)(*mean) if do else (ctypes.c_float * 3)()
-    s = (ctypes.c_float * 3)(*std) if do else (ctypes.c_float * 3)(1, 1, 1)
-    E.check(E.lib().rr_stem_conv_pool_ragged(ptrs, ext, len(images), h, w, int(u8), m, s, int(do), E.ptr(wpk),
+    m, s, do = _stem_norm_arrays(mean, std)
+    E.check(E.lib().rr_stem_conv_pool_ragged(ptrs, ext, len(images), h, w, int(u8), m, s, do, E.ptr(wpk),
                                              E.ptr(scale), E.ptr(shift), E.RR_ACT_LEAKY if leaky else E.RR_ACT_IDENTITY,
                                              float(slope), E.ptr(y), hp, wp, E.dtype_code(wpk.dtype), _st()),
             "rr_stem_conv_pool_ragged")

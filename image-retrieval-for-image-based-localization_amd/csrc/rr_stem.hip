@@ -1,4 +1,4 @@
-// librr.so — fused ResNet stem (bf16): normalise + conv1 7x7/s2/p3 (3 -> 64)
+// librr.so — fused ResNet stem (bf16 / fp16): normalise + conv1 7x7/s2/p3 (3 -> 64)
 // + BN affine + activation + max-pool 3x3/s2/p1, one kernel.
 //
 // Replaces the reference's mod1 = Sequential(conv1, bn1, pool1)
@@ -7,20 +7,42 @@
 // (conv write + pool read: 4x the pooled bytes) and runs the 7x7 im2col
 // through the generic LDS-DMA engine at 8 padded channels per tap.
 //
-// Layout of the work, per block (one per CU, persistent over tiles):
-//   * pooled tile PH x PW  <-  stem tile (2PH+1) x (2PW+1)  <-  input patch
-//     (4PH+7) x (4PW+8) pixels of the fp32 NCHW image, normalised on the fly
-//     and staged in LDS as bf16 [row][col][4 ch] (8 B / pixel, channel 3 = 0);
-//     the next tile's patch is fetched into VGPRs while this tile computes;
-//   * K = 7 kh x 8 kw x 4 ch = 224 (kw = 7 and ch = 3 carry zero weights), so
-//     an MFMA K-step is one kernel row and a lane's 8 k-values are two
-//     horizontally adjacent input pixels: one aligned 16-B ds_read;
-//   * weights (PERM32 row order, [64][256] bf16) live in VGPRs for the whole
-//     launch (4 channel fragments x 7 K-steps);
-//   * epilogue: BN + activation -> bf16 stem tile in LDS (-inf outside the
-//     stem map, i.e. max-pool padding), then the 3x3/s2 max, 16-B stores.
+// Every kernel here is one block per CU, persistent over pooled tiles: the
+// input patch of a tile is normalised on the fly and staged in LDS as 16-bit
+// values, the next tile's patch is fetched into VGPRs while this tile computes,
+// and the packed weights ([64 PERM32 rows][448], see WROW) stay in VGPRs for
+// the whole launch.  Zero padding is applied after normalisation; uint8 pixels
+// are x / 255 in IEEE division (torchvision to_tensor).
+//
+// Map of the file:
+//   shared helpers   tile_origin (tile -> image and pooled origin; every kernel),
+//                    image_src / image_rsrc (an image's base, extent and raw
+//                    buffer, dense or ragged; OOBO, the out-of-image offset; v2
+//                    and both layouts), load_wfrag (weight fragments with the
+//                    sign flip of pool-before-epilogue; the frame)
+//   v1  k_stem_pool  epilogue on every stem pixel, pooling through LDS order
+//                    keys; 4 x 32 tiles.  The only kernel for odd stem maps
+//   v2  k_stem_pool2 pool BEFORE the epilogue (exact, see there), pooling by
+//                    DPP row shifts, LDS scale tables; 8 x 56 tiles
+//   k_stem_lane      the frame of the lane-local kernels: v2's tile with the
+//                    MFMA operands swapped, so pooling and the epilogue run
+//                    lane-locally.  It owns the byte table, the weight
+//                    fragments, the part-wise patch fill schedule, the
+//                    persistent tile loop, the stem-row walk, the pooling tail,
+//                    the epilogue and the stores; a patch layout supplies how
+//                    the patch lies in LDS: its fill and the operand read
+//     RowPatch       v3: K = kernel rows (7 K-steps), pixel pairs of 16 B, a
+//                    read-ahead of the next row's first operands; FF = the
+//                    interior fast fill
+//     S2dPatch       v4: K in space-to-depth form (6 K-steps), s2d pixels of 24 B
+//   k_stem_pack      conv1 weights -> the packed layout of both K orders
+//
+// RR_TUNE_STEM (even stem maps; odd ones always run v1):
+//   0 v1 | 1 v2 (ragged: as 2) | 2 RowPatch, fill in 3 parts (the default) |
+//   3 / 4 RowPatch, 2 / 5 parts | 5 S2dPatch, 3 parts | 6 RowPatch FF, 3 parts
 // Results equal the unfused path up to fp32 summation order inside the conv
-// (the max-pool is exact on the same bf16 values).
+// (the max-pool is exact on the same 16-bit values); v2 and RowPatch are equal
+// bit for bit, S2dPatch sums the same products in another order.
 #include "rr_internal.h"
 
 #include <type_traits>
@@ -60,6 +82,71 @@ __device__ __forceinline__ unsigned bf16_key2(unsigned w) {
     return w ^ (neg * 0x7FFFu);
 }
 
+// ---------------------------------------------------------------------------
+// Shared by every kernel below.
+
+// Tile t of a launch over (image, tile row, tile column) -> its image and the
+// pooled pixel its PH x PW tile starts at.
+template <int PH, int PW>
+__device__ __forceinline__ void tile_origin(int t, int tiles_w, int tiles_hw, int& img, int& ph0, int& pw0) {
+    img = t / tiles_hw;
+    const int rem = t - img * tiles_hw;
+    const int th = rem / tiles_w;
+    ph0 = th * PH;
+    pw0 = (rem - th * tiles_w) * PW;
+}
+
+// Image `img` of a launch: the address of its 3 planes and its own extent.  A
+// same-size batch (NoTab) has them in a.x at the batch map's h x w; a ragged
+// batch has each image at its own address with its own extent: map pixels past
+// it read 0 -- the batch pad, normalised like any pixel.
+struct ImageSrc {
+    const char* base;
+    int h, w;
+};
+template <bool U8, typename TAB>
+__device__ __forceinline__ ImageSrc image_src(const StemArgs& a, const TAB& rt, int img) {
+    if constexpr (std::is_same<TAB, RaggedTab>::value)
+        return {(const char*)rt.p[img], rt.h[img], rt.w[img]};
+    else
+        return {(const char*)a.x + (long long)img * 3 * ((long long)a.h * a.w_) * (U8 ? 1 : 4), a.h, a.w_};
+}
+// The image as one raw buffer (3 planes) with 32-bit byte offsets.  A pixel
+// outside the image gets the offset OOBO, past any buffer (reads 0) -- never a
+// negative one -- and is zeroed after normalisation where it is outside the
+// batch map too.
+constexpr unsigned OOBO = 0x80000000u;
+template <bool U8>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t image_rsrc(const ImageSrc& s) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)s.base, (short)0, (int)(3 * (s.h * s.w) * (U8 ? 1 : 4)),
+                                             0x00020000);
+}
+
+// KS K-steps of packed weight row R from chunk `woff` on, this lane's 16-B
+// chunk q of each; `neg`: the row negated (the sign bit of every 16-bit
+// element), for the kernels that pool before the epilogue.
+template <int KS>
+__device__ __forceinline__ void load_wfrag(const uint4* w, int R, int woff, int q, bool neg, uint4 (&reg)[KS]) {
+    const unsigned flip = neg ? 0x80008000u : 0u;
+#pragma unroll
+    for (int m = 0; m < KS; ++m) {
+        uint4 v = w[R * WROW + woff + m * 4 + q];
+        v.x ^= flip; v.y ^= flip; v.z ^= flip; v.w ^= flip;
+        reg[m] = v;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Stem v1.  Layout of the work, per block:
+//   * pooled tile PH x PW  <-  stem tile (2PH+1) x (2PW+1)  <-  input patch
+//     (4PH+7) x (4PW+8) pixels of the fp32 NCHW image, normalised on the fly
+//     and staged in LDS as bf16 [row][col][4 ch] (8 B / pixel, channel 3 = 0);
+//   * K = 7 kh x 8 kw x 4 ch = 224 (kw = 7 and ch = 3 carry zero weights), so
+//     an MFMA K-step is one kernel row and a lane's 8 k-values are two
+//     horizontally adjacent input pixels: one aligned 16-B ds_read;
+//   * weights live in VGPRs (4 channel fragments x 7 K-steps);
+//   * epilogue: BN + activation -> bf16 stem tile in LDS (-inf outside the
+//     stem map, i.e. max-pool padding), then the 3x3/s2 max, 16-B stores.
 template <int PH, int PW, typename HT, bool U8 = false, typename TAB = NoTab>
 __global__ void __launch_bounds__(NT) k_stem_pool(StemArgs a, TAB rt, int tiles_w, int tiles_hw, int ntiles) {
     constexpr bool RG = std::is_same<TAB, RaggedTab>::value;
@@ -91,21 +178,15 @@ __global__ void __launch_bounds__(NT) k_stem_pool(StemArgs a, TAB rt, int tiles_
 #pragma unroll
         for (int m = 0; m < 7; ++m) areg[i][m] = a.w[(i * 16 + r16) * WROW + m * 4 + q];
 
-    auto tile_origin = [&](int t, int& img, int& ph0, int& pw0) {
-        img = t / tiles_hw;
-        const int rem = t - img * tiles_hw;
-        const int th = rem / tiles_w;
-        ph0 = th * PH;
-        pw0 = (rem - th * tiles_w) * PW;
-    };
-
     float pf[SPT][3];
     auto fill_load = [&](int t) {
         int img, ph0, pw0;
-        tile_origin(t, img, ph0, pw0);
+        tile_origin<PH, PW>(t, tiles_w, tiles_hw, img, ph0, pw0);
         const int ir0 = 4 * ph0 - 5, ic0 = 4 * pw0 - 5;  // = 2 * (2 * p0 - 1) - 3
         // the image's own extent (ragged: its pixels at its own address; map pixels
-        // past it read 0 -- the batch pad, normalised in fill_store)
+        // past it read 0 -- the batch pad, normalised in fill_store).  Plain loads at
+        // 64-bit element indices from a.x, not image_src's per-image base: this is the
+        // kernel of the odd maps, and that form changes its tile loop
         const void* ib = a.x;
         int hi = H, wi = W;
         long long ibase = (long long)img * 3 * plane, iplane = plane;
@@ -134,7 +215,7 @@ __global__ void __launch_bounds__(NT) k_stem_pool(StemArgs a, TAB rt, int tiles_
     };
     auto fill_store = [&](int t, int buf) {
         int img, ph0, pw0;
-        tile_origin(t, img, ph0, pw0);
+        tile_origin<PH, PW>(t, tiles_w, tiles_hw, img, ph0, pw0);
         const int ir0 = 4 * ph0 - 5, ic0 = 4 * pw0 - 5;
 #pragma unroll
         for (int u = 0; u < SPT; ++u) {
@@ -163,7 +244,7 @@ __global__ void __launch_bounds__(NT) k_stem_pool(StemArgs a, TAB rt, int tiles_
         const int tn = t + gridDim.x;
         if (tn < ntiles) fill_load(tn);
         int img, ph0, pw0;
-        tile_origin(t, img, ph0, pw0);
+        tile_origin<PH, PW>(t, tiles_w, tiles_hw, img, ph0, pw0);
         const int sr0 = 2 * ph0 - 1, sc0 = 2 * pw0 - 1;
         const char* patch = sP[cur];
         for (int f = wave; f < NF; f += NT / 64) {
@@ -248,6 +329,14 @@ __global__ void __launch_bounds__(NT) k_stem_pool(StemArgs a, TAB rt, int tiles_
 }
 
 // ---------------------------------------------------------------------------
+// The 8 x 56 tile of v2 and of the lane-local kernels: wave w owns stem columns
+// 14w .. 14w + 15 (one 16-pixel fragment per stem row, 2 columns of overlap: 7
+// pooled columns) and walks the 17 stem rows top to bottom.
+constexpr int LPH = 8, LPW = 56, LSRN = 2 * LPH + 1, LCB = 14;
+constexpr int LSCN = LCB * 7 + 16;  // 114 stem columns
+static_assert(LPW == 7 * (NT / 64), "one 7-pooled-column block per wave");
+
+// ---------------------------------------------------------------------------
 // Stem v2: pool BEFORE the epilogue.  f(v) = round16(act(|s| * v + h)) is
 // non-decreasing in v (fma with |s| >= 0, leaky with slope in [0, 1], RNE),
 // so max-pool(f(conv)) == f(max-pool(conv)) exactly.  Output channels whose
@@ -256,10 +345,7 @@ __global__ void __launch_bounds__(NT) k_stem_pool(StemArgs a, TAB rt, int tiles_
 // accumulator is exactly -conv) and use |s|: every value equals the select-
 // form result of k_stem_pool bit for bit, and BN + activation + packing run
 // on the 4x fewer pooled pixels only.
-// Work layout: a tile is PH = 8 pooled rows x PW = 56 pooled cols; wave w
-// owns stem columns 14w .. 14w + 15 (one 16-pixel B fragment per stem row,
-// 2 columns of overlap: 7 pooled columns) and walks the 17 stem rows top to
-// bottom: the vertical 3-max of each pooled row is a per-lane max3 over the
+// Work layout: the vertical 3-max of each pooled row is a per-lane max3 over the
 // accumulators of 3 consecutive stem rows (kept in VGPRs), the horizontal
 // 3-max two DPP row shifts (lane i <- lanes i+1, i+2 of the 16-pixel row).
 // No LDS round trip and no barrier for the pooling; one barrier per tile for
@@ -267,14 +353,12 @@ __global__ void __launch_bounds__(NT) k_stem_pool(StemArgs a, TAB rt, int tiles_
 // [row][col][4 ch], 39 x 234 pixels).
 template <typename HT, bool U8>
 __global__ void __launch_bounds__(NT) k_stem_pool2(StemArgs a, int tiles_w, int tiles_hw, int ntiles) {
-    constexpr int PH = 8, PW = 56, SRN = 2 * PH + 1, CB = 14;
-    constexpr int IR = 2 * (SRN - 1) + 7;            // 39 input rows
-    constexpr int SCN = CB * 7 + 16;                 // 114 stem columns
-    constexpr int IC = 2 * (SCN - 1) + 8;            // 234 input columns (even: 16-B pixel pairs)
+    constexpr int PH = LPH, PW = LPW, CB = LCB;
+    constexpr int IR = 2 * (LSRN - 1) + 7;           // 39 input rows
+    constexpr int IC = 2 * (LSCN - 1) + 8;           // 234 input columns (even: 16-B pixel pairs)
     constexpr int HIC = IC / 2;
     constexpr int NPAIR = IR * HIC, PPT = (NPAIR + NT - 1) / NT;
     constexpr int PATCH = IR * IC * 8;
-    static_assert(PW == 7 * (NT / 64), "one 7-pooled-column block per wave");
     __shared__ __attribute__((aligned(16))) char sP[2][PATCH];
     __shared__ __attribute__((aligned(16))) float sS[64], sH[64];
 
@@ -282,14 +366,14 @@ __global__ void __launch_bounds__(NT) k_stem_pool2(StemArgs a, int tiles_w, int 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r16 = lane & 15, q = lane >> 4;
     const int H = a.h, W = a.w_;
-    const long long plane = (long long)H * W;
 
     if (tid < 64) {
         sS[tid] = fabsf(a.scale[tid]);
         sH[tid] = a.shift[tid];
     }
     // weights -> VGPRs (fragment i = packed rows 16i .. 16i+15, K-step m = kernel row),
-    // rows of negative-scale channels negated (sign bit of every 16-bit element)
+    // rows of negative-scale channels negated.  load_wfrag's loop, spelled out: through the
+    // helper this kernel, at its 256 VGPRs, spills 44 VGPRs instead of 29
     uint4 areg[4][7];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -302,14 +386,6 @@ __global__ void __launch_bounds__(NT) k_stem_pool2(StemArgs a, int tiles_w, int 
         }
     }
 
-    auto tile_origin = [&](int t, int& img, int& ph0, int& pw0) {
-        img = t / tiles_hw;
-        const int rem = t - img * tiles_hw;
-        const int th = rem / tiles_w;
-        ph0 = th * PH;
-        pw0 = (rem - th * tiles_w) * PW;
-    };
-
     // patch fill: pixel pairs (2 adjacent input columns) -> one 16-B LDS store;
     // in two halves (pairs u < PH1, u >= PH1) so only half the raw pixels are
     // live in VGPRs while the MFMAs run
@@ -317,16 +393,12 @@ __global__ void __launch_bounds__(NT) k_stem_pool2(StemArgs a, int tiles_w, int 
     float pf[PH1][6];
     auto fill_load = [&](int t, int half) {
         int img, ph0, pw0;
-        tile_origin(t, img, ph0, pw0);
+        tile_origin<PH, PW>(t, tiles_w, tiles_hw, img, ph0, pw0);
         const int ir0 = 4 * ph0 - 5, ic0 = 4 * pw0 - 5;
-        // one raw buffer per image (3 planes) with 32-bit offsets; a pixel outside
-        // the image gets an offset past the buffer (reads 0) -- never a negative
-        // one -- and is zeroed after normalisation in fill_store anyway
         constexpr int ESZ = U8 ? 1 : 4;
-        constexpr unsigned OOBO = 0x80000000u;
-        const char* ib = (const char*)a.x + (long long)img * 3 * plane * ESZ;
-        const __amdgpu_buffer_rsrc_t rs =
-            __builtin_amdgcn_make_buffer_rsrc((void*)ib, (short)0, (int)(3 * plane * ESZ), 0x00020000);
+        const ImageSrc s = image_src<U8>(a, NoTab{}, img);
+        const int iplane = s.h * s.w;
+        const __amdgpu_buffer_rsrc_t rs = image_rsrc<U8>(s);
 #pragma unroll
         for (int uu = 0; uu < PH1; ++uu) {
             const int u = half * PH1 + uu;
@@ -341,7 +413,7 @@ __global__ void __launch_bounds__(NT) k_stem_pool2(StemArgs a, int tiles_w, int 
             const unsigned off1 = rok && (unsigned)(iw + 1) < (unsigned)W ? (unsigned)(o + ESZ) : OOBO;
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) {
-                const unsigned po = (unsigned)(ch * (int)plane * ESZ);
+                const unsigned po = (unsigned)(ch * iplane * ESZ);
                 if constexpr (U8) {  // IEEE division: the same float as torch's / numpy's x / 255
                     pf[uu][2 * ch] = (float)__builtin_amdgcn_raw_buffer_load_b8(rs, (int)(off0 + po), 0, 0) / 255.f;
                     pf[uu][2 * ch + 1] = (float)__builtin_amdgcn_raw_buffer_load_b8(rs, (int)(off1 + po), 0, 0) / 255.f;
@@ -354,7 +426,7 @@ __global__ void __launch_bounds__(NT) k_stem_pool2(StemArgs a, int tiles_w, int 
     };
     auto fill_store = [&](int t, int buf, int half) {
         int img, ph0, pw0;
-        tile_origin(t, img, ph0, pw0);
+        tile_origin<PH, PW>(t, tiles_w, tiles_hw, img, ph0, pw0);
         const int ir0 = 4 * ph0 - 5, ic0 = 4 * pw0 - 5;
 #pragma unroll
         for (int uu = 0; uu < PH1; ++uu) {
@@ -396,7 +468,7 @@ __global__ void __launch_bounds__(NT) k_stem_pool2(StemArgs a, int tiles_w, int 
         const int tn = t + gridDim.x;
         if (tn < ntiles) fill_load(tn, 0);
         int img, ph0, pw0;
-        tile_origin(t, img, ph0, pw0);
+        tile_origin<PH, PW>(t, tiles_w, tiles_hw, img, ph0, pw0);
         const int cb = CB * wave;
         const char* pb = sP[cur] + (2 * (cb + r16) + 2 * q) * 8;
         // this wave's pooled columns: skip the wave when all of them lie past the map
@@ -490,113 +562,85 @@ __global__ void __launch_bounds__(NT) k_stem_pool2(StemArgs a, int tiles_w, int 
 
 
 // ---------------------------------------------------------------------------
-// Stem v3: the v2 tile and pool-before-epilogue, with the MFMA operands
-// swapped so pooling and the epilogue run lane-locally on useful values only.
-// A = 16 stem pixels (rows), B = 16 output channels (columns): lane (j, q)
-// holds pixels 4q..4q+3 of output channel 4j + f in fragment f.  The wave's
-// 16 pixels are stem columns 14w + 4q + e: group q pools pooled columns
-// 7w + 2q (its pixels e = 0,1,2) and 7w + 2q + 1 (e = 2,3 and pixel e = 0 of
-// group q + 1, one ds_bpermute from lane + 16; group 3's second column belongs
-// to the next wave and is dropped).  Per pooled row a lane runs 16 + 8 max3,
-// BN + activation on 8 values (4 consecutive channels of 2 pooled pixels) and
-// two 8-B stores -- v2 shifted 32 values by DPP and ran the epilogue on every
-// lane of which 7 of 16 stored.  Per-lane channel constants live in VGPRs.
-// Patch fill: float pixels are normalised as packed pairs (v_pk_add/mul_f32,
-// the same IEEE operations); uint8 pixels go through a per-channel LDS table
-// of the normalised value of each byte (x / 255 in IEEE division, then the
-// same normalisation), computed once per block.  Same values as v2 bit for
-// bit when the swapped MFMA accumulates in the same order.
+// The lane-local kernels (v3, v4): the v2 tile and pool-before-epilogue, with
+// the MFMA operands swapped so pooling and the epilogue run lane-locally on
+// useful values only.  A = 16 stem pixels (rows), B = 16 output channels
+// (columns): lane (j, q) holds pixels 4q..4q+3 of output channel 4j + f in
+// fragment f.  The wave's 16 pixels are stem columns 14w + 4q + e: group q
+// pools pooled columns 7w + 2q (its pixels e = 0,1,2) and 7w + 2q + 1 (e = 2,3
+// and pixel e = 0 of group q + 1, one ds_bpermute from lane + 16; group 3's
+// second column belongs to the next wave and is dropped).  Per pooled row a
+// lane runs 16 + 8 max3, BN + activation on 8 values (4 consecutive channels of
+// 2 pooled pixels) and two 8-B stores -- v2 shifted 32 values by DPP and ran the
+// epilogue on every lane of which 7 of 16 stored.  Per-lane channel constants
+// live in VGPRs.  uint8 pixels go through a per-channel LDS table of the
+// normalised value of each byte (x / 255 in IEEE division, then the same
+// normalisation), computed once per block.
+//
+// A patch layout is a struct of constants and __device__ __forceinline__
+// members, one object per thread:
+//   PATCH, KSTEPS, WOFF       bytes of one LDS patch buffer; MFMA K-steps and
+//                             the first weight chunk of its K order
+//   load(img, ir0, ic0, part) part `part` of NPART of the raw pixels of the
+//                             patch whose input rectangle starts at (ir0, ic0)
+//                             of image img -> VGPRs
+//   store(..., buf, part)     those pixels, normalised and packed -> LDS buffer buf
+//   at(buf, col)              this lane's pixel: stem column `col` of the tile in buffer buf
+//   operand(r, m, use_pre)    the lane's 16 B of K-step m of stem row r
+//   preload(r)                read-ahead hook: operands of row r that operand(r, ., true)
+//                             then takes from VGPRs
+
 // first pixel of the 8-B load that carries pixel pair (iw, iw + 1) of an image
 // row of wi pixels: the pair itself inside the row, the row's first / last two
 // pixels where the pair overhangs it (so a pair load never leaves its row when
 // wi >= 2; a 1-pixel row loads its pixel and the next element)
 __device__ __forceinline__ int pair_base(int iw, int wi) { return max(min(iw, wi - 2), 0); }
 
+// Kernel-row layout (v3): the patch is 39 x 234 input pixels of 8 B
+// ([row][col][4 ch], channel 3 = 0), an MFMA K-step is one kernel row and a
+// lane's 8 k-values are two adjacent pixels: one aligned 16-B ds_read.  The
+// fill's work item is a pixel pair (one 16-B LDS store): float pixels are
+// loaded and normalised as packed pairs (v_pk_add/mul_f32, the same IEEE
+// operations), uint8 pixels one byte at a time.  Same values as v2 bit for bit
+// (the swapped MFMA accumulates in the same order).
 // FF (fast fill): a wave-instruction of the patch fill whose pixel pairs all lie inside the
 // image row and the batch map (every pair of an interior tile, most of a border tile's) skips
 // the border selects: the same values, ~1/4 of the vector instructions per pair.
-template <typename HT, bool U8, int NPART, typename TAB = NoTab, bool FF = false>
-__global__ void __launch_bounds__(NT) k_stem_pool3(StemArgs a, TAB rt, int tiles_w, int tiles_hw, int ntiles) {
-    constexpr bool RG = std::is_same<TAB, RaggedTab>::value;
-    constexpr int PH = 8, PW = 56, SRN = 2 * PH + 1, CB = 14;
-    constexpr int IR = 2 * (SRN - 1) + 7;            // 39 input rows
-    constexpr int SCN = CB * 7 + 16;                 // 114 stem columns
-    constexpr int IC = 2 * (SCN - 1) + 8;            // 234 input columns (even: 16-B pixel pairs)
-    constexpr int HIC = IC / 2;
-    constexpr int NPAIR = IR * HIC, PPT = (NPAIR + NT - 1) / NT;
-    constexpr int PATCH = IR * IC * 8;
-    static_assert(PW == 7 * (NT / 64), "one 7-pooled-column block per wave");
-    constexpr int NPRE = 2;  // K-steps of the next odd stem row read ahead (of 7)
+template <typename HT, bool U8, int NPART, typename TAB, bool FF>
+struct RowPatchT {
+    static constexpr bool RG = std::is_same<TAB, RaggedTab>::value;
+    static constexpr int IR = 2 * (LSRN - 1) + 7;    // 39 input rows
+    static constexpr int IC = 2 * (LSCN - 1) + 8;    // 234 input columns (even: 16-B pixel pairs)
+    static constexpr int HIC = IC / 2;
+    static constexpr int NPAIR = IR * HIC, PPT = (NPAIR + NT - 1) / NT;
+    static constexpr int PATCH = IR * IC * 8;
+    static constexpr int KSTEPS = 7, WOFF = 0;
+    static constexpr int NPRE = 2;  // K-steps of the next odd stem row read ahead (of 7)
+    // NPART parts, so only a third of the raw pixels is live in VGPRs while the
+    // MFMAs run (v2's halves spilled ~30 VGPRs)
+    static constexpr int PH1 = (PPT + NPART - 1) / NPART;
     typedef __attribute__((ext_vector_type(2))) float f2;
-    __shared__ __attribute__((aligned(16))) char sP[2][PATCH];
-    __shared__ float sL[U8 ? 3 * 256 : 1];
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r16 = lane & 15, q = lane >> 4;
-    const int H = a.h, W = a.w_;
-    const long long plane = (long long)H * W;
-
-    if constexpr (U8) {
-        for (int i = tid; i < 3 * 256; i += NT) {
-            const int ch = i >> 8;
-            const float x = (float)(i & 255) / 255.f;  // IEEE division = to_tensor
-            sL[i] = a.do_norm ? (x - a.mean[ch]) * a.rstd[ch] : x;
-        }
-    }
-    // B fragments: channel 4 * r16 + f of fragment f, K-step m = kernel row m;
-    // negative-scale channels negated (pool before the epilogue, see v2)
-    uint4 breg[4][7];
-    float sc[4], sh[4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-        const int c = 4 * r16 + f;
-        const int R = (c & ~31) | (((c >> 2) & 1) << 4) | (((c >> 3) & 3) << 2) | (c & 3);  // perm32_channel^-1
-        const float s = a.scale[c];
-        sc[f] = fabsf(s);
-        sh[f] = a.shift[c];
-        const unsigned flip = s < 0.f ? 0x80008000u : 0u;
-#pragma unroll
-        for (int m = 0; m < 7; ++m) {
-            uint4 w = a.w[R * WROW + m * 4 + q];
-            w.x ^= flip; w.y ^= flip; w.z ^= flip; w.w ^= flip;
-            breg[f][m] = w;
-        }
-    }
-
-    auto tile_origin = [&](int t, int& img, int& ph0, int& pw0) {
-        img = t / tiles_hw;
-        const int rem = t - img * tiles_hw;
-        const int th = rem / tiles_w;
-        ph0 = th * PH;
-        pw0 = (rem - th * tiles_w) * PW;
-    };
-
-    // patch fill in NPART parts, so only a third of the raw pixels is live in
-    // VGPRs while the MFMAs run (v2's halves spilled ~30 VGPRs)
-    constexpr int PH1 = (PPT + NPART - 1) / NPART;
     typedef typename std::conditional<U8, int, float>::type PT;
+
+    const StemArgs& a;
+    const TAB& rt;
+    char* const sP;          // [2][PATCH]
+    const float* const sL;   // the byte table
+    const int tid, q;
     PT pf[PH1][6];
-    auto fill_load = [&](int t, int half) {
-        int img, ph0, pw0;
-        tile_origin(t, img, ph0, pw0);
-        const int ir0 = 4 * ph0 - 5, ic0 = 4 * pw0 - 5;
+    uint4 pre[NPRE];
+    const char* pb;
+
+    __device__ __forceinline__ RowPatchT(const StemArgs& a_, const TAB& rt_, char* sP_, const float* sL_, int tid_,
+                                         int q_)
+        : a(a_), rt(rt_), sP(sP_), sL(sL_), tid(tid_), q(q_) {}
+
+    __device__ __forceinline__ void load(int img, int ir0, int ic0, int half) {
         constexpr int ESZ = U8 ? 1 : 4;
-        constexpr unsigned OOBO = 0x80000000u;
-        // the image's own extent and planes (ragged: at its own address; map
-        // pixels past its extent read 0 -- the batch pad, normalised in fill_store)
-        const char* ib;
-        int hi = H, wi = W;
-        if constexpr (RG) {
-            ib = (const char*)rt.p[img];
-            hi = rt.h[img];
-            wi = rt.w[img];
-        } else {
-            ib = (const char*)a.x + (long long)img * 3 * plane * ESZ;
-        }
+        const ImageSrc s = image_src<U8>(a, rt, img);
+        const int hi = s.h, wi = s.w;
         const int iplane = hi * wi;
-        const __amdgpu_buffer_rsrc_t rs =
-            __builtin_amdgcn_make_buffer_rsrc((void*)ib, (short)0, (int)(3 * iplane * ESZ), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = image_rsrc<U8>(s);
 #pragma unroll
         for (int uu = 0; uu < PH1; ++uu) {
             const int u = half * PH1 + uu;
@@ -618,7 +662,7 @@ __global__ void __launch_bounds__(NT) k_stem_pool3(StemArgs a, TAB rt, int tiles
                     pf[uu][2 * ch + 1] = ch * 256 + (int)__builtin_amdgcn_raw_buffer_load_b8(rs, (int)(off1 + po), 0, 0);
                 }
             } else {
-                // float pixels: one 8-B load per pixel pair at pair_base (fill_store
+                // float pixels: one 8-B load per pixel pair at pair_base (store
                 // picks the pair's values); for a 1-pixel row the second dword may
                 // pass the buffer end, which the per-dword range check reads as 0
                 // (tools/oob_probe.hip) -- that value is never used
@@ -633,11 +677,10 @@ __global__ void __launch_bounds__(NT) k_stem_pool3(StemArgs a, TAB rt, int tiles
                 }
             }
         }
-    };
-    auto fill_store = [&](int t, int buf, int half) {
-        int img, ph0, pw0;
-        tile_origin(t, img, ph0, pw0);
-        const int ir0 = 4 * ph0 - 5, ic0 = 4 * pw0 - 5;
+    }
+
+    __device__ __forceinline__ void store(int img, int ir0, int ic0, int buf, int half) {
+        const int H = a.h, W = a.w_;
 #pragma unroll
         for (int uu = 0; uu < PH1; ++uu) {
             const int u = half * PH1 + uu;
@@ -649,7 +692,7 @@ __global__ void __launch_bounds__(NT) k_stem_pool3(StemArgs a, TAB rt, int tiles
             const bool rok = (unsigned)(ir0 + r) < (unsigned)H;
             const bool ok0 = rok && (unsigned)(ic0 + c) < (unsigned)W;
             const bool ok1 = rok && (unsigned)(ic0 + c + 1) < (unsigned)W;
-            // float pixels (fill_load's pair loads): which loaded value is which
+            // float pixels (load's pair loads): which loaded value is which
             // pixel; pixels outside the image row read raw 0 (the ragged batch pad)
             const int iw = ic0 + c;
             int wi = W;
@@ -675,7 +718,7 @@ __global__ void __launch_bounds__(NT) k_stem_pool3(StemArgs a, TAB rt, int tiles
                     o.y = H16<HT>::pack2(v[2].x, 0.f);
                     o.z = H16<HT>::pack2(v[0].y, v[1].y);
                     o.w = H16<HT>::pack2(v[2].y, 0.f);
-                    *reinterpret_cast<uint4*>(sP[buf] + (r * IC + c) * 8) = o;
+                    *reinterpret_cast<uint4*>(sP + buf * PATCH + (r * IC + c) * 8) = o;
                     continue;
                 }
             }
@@ -699,216 +742,80 @@ __global__ void __launch_bounds__(NT) k_stem_pool3(StemArgs a, TAB rt, int tiles
             o.y = H16<HT>::pack2(v[2].x, 0.f);
             o.z = H16<HT>::pack2(v[0].y, v[1].y);
             o.w = H16<HT>::pack2(v[2].y, 0.f);
-            *reinterpret_cast<uint4*>(sP[buf] + (r * IC + c) * 8) = o;
+            *reinterpret_cast<uint4*>(sP + buf * PATCH + (r * IC + c) * 8) = o;
         }
-    };
-
-    const float slope = a.leaky ? a.slope : 1.f;  // identity == leaky with slope 1
-    const float NINF = -__builtin_inff();
-    int t = blockIdx.x;
-    if (t >= ntiles) return;
-    if constexpr (U8) __syncthreads();  // byte table
-#pragma unroll
-    for (int part = 0; part < NPART; ++part) {
-        fill_load(t, part);
-        fill_store(t, 0, part);
     }
-    __syncthreads();
-    const int nb_addr = ((lane + 16) & 63) * 4;
-    int cur = 0;
-    for (; t < ntiles; t += gridDim.x, cur ^= 1) {
-        const int tn = t + gridDim.x;
-        if (tn < ntiles) fill_load(tn, 0);
-        int img, ph0, pw0;
-        tile_origin(t, img, ph0, pw0);
-        const char* pb = sP[cur] + (2 * (CB * wave + r16) + 2 * q) * 8;
-        const bool active = pw0 + 7 * wave < a.wp;
-        // even stem dims (host-checked): the only stem pixels outside the map that
-        // feed stored outputs are row -1 (top tiles) and column -1 (left tiles:
-        // wave 0, pixel 0 = lanes of group 0, element 0)
-        const bool left = pw0 == 0 && wave == 0;
-        const int pc0 = 7 * wave + 2 * q;
-        const bool st0 = pw0 + pc0 < a.wp, st1 = q < 3 && pw0 + pc0 + 1 < a.wp;
-        // the first NPRE K-steps' patch fragments of the next odd stem row are read
-        // before the pooling tail of the current pooled row: their LDS latency
-        // overlaps the tail instead of opening the next row's MFMAs
-        uint4 pre[NPRE];
-        auto preload = [&](int r) {
-            const char* rb = pb + r * (2 * IC * 8);
+
+    __device__ __forceinline__ void at(int buf, int col) { pb = sP + buf * PATCH + (2 * col + 2 * q) * 8; }
+
+    // the first NPRE K-steps' patch fragments of the next odd stem row are read
+    // before the pooling tail of the current pooled row: their LDS latency
+    // overlaps the tail instead of opening the next row's MFMAs
+    __device__ __forceinline__ void preload(int r) {
+        const char* rb = pb + r * (2 * IC * 8);
 #pragma unroll
-            for (int m = 0; m < NPRE; ++m) pre[m] = *reinterpret_cast<const uint4*>(rb + m * IC * 8);
-        };
-        auto stem_row = [&](int r, h16_f32x4_t (&acc)[4], bool use_pre) {
-#pragma unroll
-            for (int f = 0; f < 4; ++f) acc[f] = (h16_f32x4_t){0.f, 0.f, 0.f, 0.f};
-            const char* rb = pb + r * (2 * IC * 8);
-#pragma unroll
-            for (int m = 0; m < 7; ++m) {
-                const uint4 px = use_pre && m < NPRE ? pre[m] : *reinterpret_cast<const uint4*>(rb + m * IC * 8);
-#pragma unroll
-                for (int f = 0; f < 4; ++f) acc[f] = H16<HT>::mfma(px, breg[f][m], acc[f]);
-            }
-        };
-        h16_f32x4_t A[4];
-        if (active) {
-            stem_row(0, A, false);
-            preload(1);
-            if (ph0 == 0) {  // stem row -1: max-pool padding
-#pragma unroll
-                for (int f = 0; f < 4; ++f) A[f] = (h16_f32x4_t){NINF, NINF, NINF, NINF};
-            }
-        }
-        for (int pr = 0; pr < PH; ++pr) {
-#pragma unroll
-            for (int part = 1; part < NPART; ++part)
-                if (pr == part * PH / NPART && tn < ntiles) {  // part - 1 of the next patch -> LDS, part in flight
-                    fill_store(tn, cur ^ 1, part - 1);
-                    fill_load(tn, part);
-                }
-            if (active) {
-                h16_f32x4_t B[4];
-                stem_row(2 * pr + 1, B, true);
-#pragma unroll
-                for (int f = 0; f < 4; ++f)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) A[f][e] = fmaxf(A[f][e], B[f][e]);  // rows 2pr, 2pr+1
-                h16_f32x4_t C[4];
-                stem_row(2 * pr + 2, C, false);
-                if (pr + 1 < PH) preload(2 * pr + 3);
-                float p0[4], p1[4];
-#pragma unroll
-                for (int f = 0; f < 4; ++f) {
-                    float m3[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) m3[e] = fmaxf(A[f][e], C[f][e]);
-                    if (left && q == 0) m3[0] = NINF;  // stem column -1: max-pool padding
-                    const float nb = __int_as_float(__builtin_amdgcn_ds_bpermute(nb_addr, __float_as_int(m3[0])));
-                    p0[f] = fmaxf(fmaxf(m3[0], m3[1]), m3[2]);
-                    p1[f] = fmaxf(fmaxf(m3[2], m3[3]), nb);
-                    A[f] = C[f];
-                }
-                if (ph0 + pr < a.hp) {
-                    bf16_t* dst = a.y + (((long long)img * a.hp + ph0 + pr) * a.wp + pw0 + pc0) * 64 + 4 * r16;
-                    auto epi = [&](const float (&p)[4]) {
-                        float v[4];
-#pragma unroll
-                        for (int f = 0; f < 4; ++f) {
-                            v[f] = p[f] * sc[f] + sh[f];
-                            v[f] = fmaxf(v[f], v[f] * slope);
-                        }
-                        return make_uint2(H16<HT>::pack2(v[0], v[1]), H16<HT>::pack2(v[2], v[3]));
-                    };
-                    if (st0) *reinterpret_cast<uint2*>(dst) = epi(p0);
-                    if (st1) *reinterpret_cast<uint2*>(dst + 64) = epi(p1);
-                }
-            }
-        }
-        if (tn < ntiles) fill_store(tn, cur ^ 1, NPART - 1);
-        __syncthreads();
+        for (int m = 0; m < NPRE; ++m) pre[m] = *reinterpret_cast<const uint4*>(rb + m * IC * 8);
     }
-}
 
+    __device__ __forceinline__ uint4 operand(int r, int m, bool use_pre) const {
+        const char* rb = pb + r * (2 * IC * 8);
+        return use_pre && m < NPRE ? pre[m] : *reinterpret_cast<const uint4*>(rb + m * IC * 8);
+    }
+};
+template <typename HT, bool U8, int NPART, typename TAB> using RowPatch = RowPatchT<HT, U8, NPART, TAB, false>;
+template <typename HT, bool U8, int NPART, typename TAB> using RowPatchFF = RowPatchT<HT, U8, NPART, TAB, true>;
 
-// ---------------------------------------------------------------------------
-// Stem v4: v3's tile, wave layout, lane-local pooling and epilogue, with the
-// conv's K in space-to-depth form.  The stride-2 7x7 conv on 3 channels is a
+// Space-to-depth layout (v4).  The stride-2 7x7 conv on 3 channels is a
 // stride-1 4x4 conv on 12-channel "s2d pixels" (2x2 input pixels x 3 channels,
 // the 8x8-padded kernel: kh = 7 / kw = 7 carry zero weights): K = 4 x 4 x 12 =
-// 192 = 6 MFMA K-steps of 32 instead of v3's 7 (7 kernel rows x 8 pixels x 4
-// channels, 66 % of it useful; here 77 %).  The patch sits in LDS as s2d pixels
+// 192 = 6 MFMA K-steps of 32 instead of the kernel rows' 7 (7 rows x 8 pixels x
+// 4 channels, 66 % of it useful; here 77 %).  The patch sits in LDS as s2d pixels
 // of 24 B ([s2d row][s2d col][a][b][ci], a / b = row / column in the pair): the 4
 // s2d pixels of one kernel row are 48 contiguous values, so a lane's 8 values of
 // a K-step (k0 = 32 m + 8 q; a kernel row holds 48, a multiple of 8) are 16
-// contiguous bytes at an 8-B aligned address: two ds_read_b64.  The tile's s2d
-// rows and columns start one before its first stem row / column (stem pixel c
-// uses s2d columns c - 1 .. c + 2); the patch (20 x 117 s2d pixels, 56 KiB) covers
-// the same input rectangle as v3's (4 ph0 - 5 .., 4 pw0 - 5 ..), plus the one input
-// row under the zero kh = 7 weights.  Same value per tap as v3 (normalised,
-// rounded to 16 bits, zero padding after normalisation); only the f32 summation
-// order of the 147 products differs.
-template <typename HT, bool U8, int NPART, typename TAB = NoTab>
-__global__ void __launch_bounds__(NT) k_stem_pool4(StemArgs a, TAB rt, int tiles_w, int tiles_hw, int ntiles) {
-    constexpr bool RG = std::is_same<TAB, RaggedTab>::value;
-    constexpr int PH = 8, PW = 56, SRN = 2 * PH + 1, CB = 14;
-    constexpr int SCN = CB * 7 + 16;                 // 114 stem columns
-    constexpr int PR = SRN + 3, PC = SCN + 3;        // 20 x 117 s2d pixels
-    constexpr int SP = 24;                           // bytes per s2d pixel (12 x 16-bit)
-    constexpr int NPIX = PR * PC, PPT = (NPIX + NT - 1) / NT;
-    constexpr int PATCH = NPIX * SP;
-    static_assert(PW == 7 * (NT / 64), "one 7-pooled-column block per wave");
-    __shared__ __attribute__((aligned(16))) char sP[2][PATCH];
-    __shared__ float sL[U8 ? 3 * 256 : 1];
+// contiguous bytes at an 8-B aligned address: two ds_read_b64.  The s2d rows and
+// columns start one before the first stem row / column (stem pixel c uses s2d
+// columns c - 1 .. c + 2); the patch (20 x 117 s2d pixels, 56 KiB) covers the
+// same input rectangle as RowPatch's, plus the one input row under the zero
+// kh = 7 weights.  Same value per tap as RowPatch (normalised, rounded to 16
+// bits, zero padding after normalisation); only the f32 summation order of the
+// 147 products differs.  The fill's work item is one s2d pixel (2 input rows x
+// 2 columns x 3 channels); no read-ahead.
+template <typename HT, bool U8, int NPART, typename TAB>
+struct S2dPatch {
+    static constexpr int PR = LSRN + 3, PC = LSCN + 3;  // 20 x 117 s2d pixels
+    static constexpr int SP = 24;                       // bytes per s2d pixel (12 x 16-bit)
+    static constexpr int NPIX = PR * PC, PPT = (NPIX + NT - 1) / NT;
+    static constexpr int PATCH = NPIX * SP;
+    static constexpr int KSTEPS = 6, WOFF = W4OFF;
+    static constexpr int PH1 = (PPT + NPART - 1) / NPART;
+    typedef typename std::conditional<U8, int, float>::type PT;
 
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r16 = lane & 15, q = lane >> 4;
-    const int H = a.h, W = a.w_;
-    const long long plane = (long long)H * W;
+    const StemArgs& a;
+    const TAB& rt;
+    char* const sP;          // [2][PATCH]
+    const float* const sL;   // the byte table
+    const int tid;
+    PT pf[PH1][12];
+    int koff[6];  // this lane's byte offset of K-step m inside the 4 x 4 s2d window of its pixel
+    const char* pb;
 
-    if constexpr (U8) {
-        for (int i = tid; i < 3 * 256; i += NT) {
-            const int ch = i >> 8;
-            const float x = (float)(i & 255) / 255.f;  // IEEE division = to_tensor
-            sL[i] = a.do_norm ? (x - a.mean[ch]) * a.rstd[ch] : x;
-        }
-    }
-    // B fragments (channel 4 * r16 + f of fragment f, s2d K-step m), negative-scale
-    // channels negated (pool before the epilogue, see v2)
-    uint4 breg[4][6];
-    float sc[4], sh[4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-        const int c = 4 * r16 + f;
-        const int R = (c & ~31) | (((c >> 2) & 1) << 4) | (((c >> 3) & 3) << 2) | (c & 3);  // perm32_channel^-1
-        const float s = a.scale[c];
-        sc[f] = fabsf(s);
-        sh[f] = a.shift[c];
-        const unsigned flip = s < 0.f ? 0x80008000u : 0u;
+    __device__ __forceinline__ S2dPatch(const StemArgs& a_, const TAB& rt_, char* sP_, const float* sL_, int tid_,
+                                        int q)
+        : a(a_), rt(rt_), sP(sP_), sL(sL_), tid(tid_) {
 #pragma unroll
         for (int m = 0; m < 6; ++m) {
-            uint4 w = a.w[R * WROW + W4OFF + m * 4 + q];
-            w.x ^= flip; w.y ^= flip; w.z ^= flip; w.w ^= flip;
-            breg[f][m] = w;
+            const int k0 = 32 * m + 8 * q;
+            koff[m] = (k0 / 48) * (PC * SP) + (k0 % 48) * 2;
         }
     }
-    // this lane's byte offset of K-step m inside the 4 x 4 s2d window of its pixel
-    int koff[6];
-#pragma unroll
-    for (int m = 0; m < 6; ++m) {
-        const int k0 = 32 * m + 8 * q;
-        koff[m] = (k0 / 48) * (PC * SP) + (k0 % 48) * 2;
-    }
 
-    auto tile_origin = [&](int t, int& img, int& ph0, int& pw0) {
-        img = t / tiles_hw;
-        const int rem = t - img * tiles_hw;
-        const int th = rem / tiles_w;
-        ph0 = th * PH;
-        pw0 = (rem - th * tiles_w) * PW;
-    };
-
-    // patch fill in NPART parts: work item = one s2d pixel (2 input rows x 2 columns x 3 channels)
-    constexpr int PH1 = (PPT + NPART - 1) / NPART;
-    typedef typename std::conditional<U8, int, float>::type PT;
-    PT pf[PH1][12];
-    auto fill_load = [&](int t, int part) {
-        int img, ph0, pw0;
-        tile_origin(t, img, ph0, pw0);
-        const int ir0 = 4 * ph0 - 5, ic0 = 4 * pw0 - 5;
+    __device__ __forceinline__ void load(int img, int ir0, int ic0, int part) {
         constexpr int ESZ = U8 ? 1 : 4;
-        constexpr unsigned OOBO = 0x80000000u;
-        const char* ib;
-        int hi = H, wi = W;
-        if constexpr (RG) {
-            ib = (const char*)rt.p[img];
-            hi = rt.h[img];
-            wi = rt.w[img];
-        } else {
-            ib = (const char*)a.x + (long long)img * 3 * plane * ESZ;
-        }
+        const ImageSrc s = image_src<U8>(a, rt, img);
+        const int hi = s.h, wi = s.w;
         const int iplane = hi * wi;
-        const __amdgpu_buffer_rsrc_t rs =
-            __builtin_amdgcn_make_buffer_rsrc((void*)ib, (short)0, (int)(3 * iplane * ESZ), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = image_rsrc<U8>(s);
 #pragma unroll
         for (int uu = 0; uu < PH1; ++uu) {
             const int u = part * PH1 + uu;
@@ -938,11 +845,10 @@ __global__ void __launch_bounds__(NT) k_stem_pool4(StemArgs a, TAB rt, int tiles
                 }
             }
         }
-    };
-    auto fill_store = [&](int t, int buf, int part) {
-        int img, ph0, pw0;
-        tile_origin(t, img, ph0, pw0);
-        const int ir0 = 4 * ph0 - 5, ic0 = 4 * pw0 - 5;
+    }
+
+    __device__ __forceinline__ void store(int img, int ir0, int ic0, int buf, int part) {
+        const int H = a.h, W = a.w_;
 #pragma unroll
         for (int uu = 0; uu < PH1; ++uu) {
             const int u = part * PH1 + uu;
@@ -964,11 +870,68 @@ __global__ void __launch_bounds__(NT) k_stem_pool4(StemArgs a, TAB rt, int tiles
                     v[e * 3 + ch] = ok ? x : 0.f;
                 }
             }
-            char* dst = sP[buf] + k * SP;
+            char* dst = sP + buf * PATCH + k * SP;
             *reinterpret_cast<uint2*>(dst) = make_uint2(H16<HT>::pack2(v[0], v[1]), H16<HT>::pack2(v[2], v[3]));
             *reinterpret_cast<uint2*>(dst + 8) = make_uint2(H16<HT>::pack2(v[4], v[5]), H16<HT>::pack2(v[6], v[7]));
             *reinterpret_cast<uint2*>(dst + 16) = make_uint2(H16<HT>::pack2(v[8], v[9]), H16<HT>::pack2(v[10], v[11]));
         }
+    }
+
+    __device__ __forceinline__ void at(int buf, int col) { pb = sP + buf * PATCH + col * SP; }
+
+    __device__ __forceinline__ void preload(int) {}
+
+    __device__ __forceinline__ uint4 operand(int r, int m, bool) const {
+        const char* rb = pb + r * (PC * SP);
+        const uint2 lo = *reinterpret_cast<const uint2*>(rb + koff[m]);
+        const uint2 hi = *reinterpret_cast<const uint2*>(rb + koff[m] + 8);
+        return make_uint4(lo.x, lo.y, hi.x, hi.y);
+    }
+};
+
+template <template <typename, bool, int, typename> class Patch, typename HT, bool U8, int NPART, typename TAB>
+__global__ void __launch_bounds__(NT) k_stem_lane(StemArgs a, TAB rt, int tiles_w, int tiles_hw, int ntiles) {
+    typedef Patch<HT, U8, NPART, TAB> P;
+    constexpr int PH = LPH, PW = LPW, CB = LCB, KS = P::KSTEPS;
+    __shared__ __attribute__((aligned(16))) char sP[2][P::PATCH];
+    __shared__ float sL[U8 ? 3 * 256 : 1];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r16 = lane & 15, q = lane >> 4;
+
+    if constexpr (U8) {
+        for (int i = tid; i < 3 * 256; i += NT) {
+            const int ch = i >> 8;
+            const float x = (float)(i & 255) / 255.f;  // IEEE division = to_tensor
+            sL[i] = a.do_norm ? (x - a.mean[ch]) * a.rstd[ch] : x;
+        }
+    }
+    // B fragments: channel 4 * r16 + f of fragment f, K-step m of the layout's K
+    // order; negative-scale channels negated (pool before the epilogue, see v2)
+    uint4 breg[4][KS];
+    float sc[4], sh[4];
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+        const int c = 4 * r16 + f;
+        const int R = (c & ~31) | (((c >> 2) & 1) << 4) | (((c >> 3) & 3) << 2) | (c & 3);  // perm32_channel^-1
+        const float s = a.scale[c];
+        sc[f] = fabsf(s);
+        sh[f] = a.shift[c];
+        load_wfrag(a.w, R, P::WOFF, q, s < 0.f, breg[f]);
+    }
+    P patch(a, rt, &sP[0][0], sL, tid, q);
+
+    // patch fill in NPART parts: the input rectangle of tile t starts at 2 * (2 * p0 - 1) - 3
+    auto fill_load = [&](int t, int part) {
+        int img, ph0, pw0;
+        tile_origin<PH, PW>(t, tiles_w, tiles_hw, img, ph0, pw0);
+        patch.load(img, 4 * ph0 - 5, 4 * pw0 - 5, part);
+    };
+    auto fill_store = [&](int t, int buf, int part) {
+        int img, ph0, pw0;
+        tile_origin<PH, PW>(t, tiles_w, tiles_hw, img, ph0, pw0);
+        patch.store(img, 4 * ph0 - 5, 4 * pw0 - 5, buf, part);
     };
 
     const float slope = a.leaky ? a.slope : 1.f;  // identity == leaky with slope 1
@@ -988,28 +951,29 @@ __global__ void __launch_bounds__(NT) k_stem_pool4(StemArgs a, TAB rt, int tiles
         const int tn = t + gridDim.x;
         if (tn < ntiles) fill_load(tn, 0);
         int img, ph0, pw0;
-        tile_origin(t, img, ph0, pw0);
-        const char* pb = sP[cur] + (CB * wave + r16) * SP;
+        tile_origin<PH, PW>(t, tiles_w, tiles_hw, img, ph0, pw0);
+        patch.at(cur, CB * wave + r16);
         const bool active = pw0 + 7 * wave < a.wp;
+        // even stem dims (host-checked): the only stem pixels outside the map that
+        // feed stored outputs are row -1 (top tiles) and column -1 (left tiles:
+        // wave 0, pixel 0 = lanes of group 0, element 0)
         const bool left = pw0 == 0 && wave == 0;
         const int pc0 = 7 * wave + 2 * q;
         const bool st0 = pw0 + pc0 < a.wp, st1 = q < 3 && pw0 + pc0 + 1 < a.wp;
-        auto stem_row = [&](int r, h16_f32x4_t (&acc)[4]) {
+        auto stem_row = [&](int r, h16_f32x4_t (&acc)[4], bool use_pre) {
 #pragma unroll
             for (int f = 0; f < 4; ++f) acc[f] = (h16_f32x4_t){0.f, 0.f, 0.f, 0.f};
-            const char* rb = pb + r * (PC * SP);
 #pragma unroll
-            for (int m = 0; m < 6; ++m) {
-                const uint2 lo = *reinterpret_cast<const uint2*>(rb + koff[m]);
-                const uint2 hi = *reinterpret_cast<const uint2*>(rb + koff[m] + 8);
-                const uint4 px = make_uint4(lo.x, lo.y, hi.x, hi.y);
+            for (int m = 0; m < KS; ++m) {
+                const uint4 px = patch.operand(r, m, use_pre);
 #pragma unroll
                 for (int f = 0; f < 4; ++f) acc[f] = H16<HT>::mfma(px, breg[f][m], acc[f]);
             }
         };
         h16_f32x4_t A[4];
         if (active) {
-            stem_row(0, A);
+            stem_row(0, A, false);
+            patch.preload(1);
             if (ph0 == 0) {  // stem row -1: max-pool padding
 #pragma unroll
                 for (int f = 0; f < 4; ++f) A[f] = (h16_f32x4_t){NINF, NINF, NINF, NINF};
@@ -1024,13 +988,14 @@ __global__ void __launch_bounds__(NT) k_stem_pool4(StemArgs a, TAB rt, int tiles
                 }
             if (active) {
                 h16_f32x4_t B[4];
-                stem_row(2 * pr + 1, B);
+                stem_row(2 * pr + 1, B, true);
 #pragma unroll
                 for (int f = 0; f < 4; ++f)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) A[f][e] = fmaxf(A[f][e], B[f][e]);  // rows 2pr, 2pr+1
                 h16_f32x4_t C[4];
-                stem_row(2 * pr + 2, C);
+                stem_row(2 * pr + 2, C, false);
+                if (pr + 1 < PH) patch.preload(2 * pr + 3);
                 float p0[4], p1[4];
 #pragma unroll
                 for (int f = 0; f < 4; ++f) {
@@ -1105,60 +1070,42 @@ extern "C" int rr_stem_pack_weights(const float* w, int c_out, int c_in, int kh,
     return check_launch("rr_stem_pack_weights");
 }
 
+template <typename T> struct TypeTag { typedef T type; };
+
 // One launch over a same-size batch (TAB = NoTab, a.x = the [n][3][h][w] buffer)
 // or over <= RAGGED_MAX images of a ragged batch (TAB = RaggedTab).
 template <bool U8, typename TAB>
 static void stem_launch(const StemArgs& a, const TAB& rt, int dtype, hipStream_t st) {
     constexpr bool RG = std::is_same<TAB, RaggedTab>::value;
     const int g_stem_cus = grid_cus();
-    // RR_TUNE_STEM: 5 space-to-depth K (v4), 2 swapped-operand lane-local pooling (v3; 3 / 4: 2 / 5 fill
-    // parts), 1 pool-before-epilogue kernel (v2), 0 k_stem_pool
-    const int mode = g_tune.stem;
-    if (mode >= 1 && a.ho % 2 == 0 && a.wo % 2 == 0) {  // v2/v3 handle the even stem maps (borders top / left)
-        constexpr int PH = 8, PW = 56;
+    const int mode = g_tune.stem;  // RR_TUNE_STEM, see the file header
+    // a persistent grid over the PH x PW pooled tiles of the batch; tab: rt for the kernels that take it
+    auto run = [&](auto kern, int PH, int PW, const auto&... tab) {
         const int tiles_w = (a.wp + PW - 1) / PW, tiles_h = (a.hp + PH - 1) / PH;
         const int ntiles = a.n * tiles_h * tiles_w;
         const int grid = ntiles < g_stem_cus ? ntiles : g_stem_cus;
-        if (mode >= 2 || RG) {  // 2: patch fill in 3 parts (default), 3: 2 parts, 4: 5 parts
-            auto launch = [&](auto kern) {
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), 0, st, a, rt, tiles_w, tiles_w * tiles_h, ntiles);
-            };
-            if (mode == 5) {
-                if (dtype == RR_F16) launch(k_stem_pool4<f16_t, U8, 3, TAB>);
-                else launch(k_stem_pool4<bf16_t, U8, 3, TAB>);
-            } else if (dtype == RR_F16) {
-                if (mode == 3) launch(k_stem_pool3<f16_t, U8, 2, TAB>);
-                else if (mode == 4) launch(k_stem_pool3<f16_t, U8, 5, TAB>);
-                else if (mode == 6) launch(k_stem_pool3<f16_t, U8, 3, TAB, true>);
-                else launch(k_stem_pool3<f16_t, U8, 3, TAB>);
-            } else {
-                if (mode == 3) launch(k_stem_pool3<bf16_t, U8, 2, TAB>);
-                else if (mode == 4) launch(k_stem_pool3<bf16_t, U8, 5, TAB>);
-                else if (mode == 6) launch(k_stem_pool3<bf16_t, U8, 3, TAB, true>);
-                else launch(k_stem_pool3<bf16_t, U8, 3, TAB>);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), 0, st, a, tab..., tiles_w, tiles_w * tiles_h, ntiles);
+    };
+    auto pick = [&](auto tag) {
+        typedef typename decltype(tag)::type HT;
+        if (mode >= 1 && a.ho % 2 == 0 && a.wo % 2 == 0) {  // v2 and the lane-local kernels handle the even
+                                                            // stem maps (borders top / left)
+            if (mode >= 2 || RG) {  // mode -> (patch layout, fill parts)
+                switch (mode) {
+                    case 3: return run(k_stem_lane<RowPatch, HT, U8, 2, TAB>, LPH, LPW, rt);
+                    case 4: return run(k_stem_lane<RowPatch, HT, U8, 5, TAB>, LPH, LPW, rt);
+                    case 5: return run(k_stem_lane<S2dPatch, HT, U8, 3, TAB>, LPH, LPW, rt);
+                    case 6: return run(k_stem_lane<RowPatchFF, HT, U8, 3, TAB>, LPH, LPW, rt);
+                    default: return run(k_stem_lane<RowPatch, HT, U8, 3, TAB>, LPH, LPW, rt);
+                }
             }
+            if constexpr (!RG) run(k_stem_pool2<HT, U8>, LPH, LPW);
             return;
         }
-        if constexpr (!RG) {
-            if (dtype == RR_F16)
-                hipLaunchKernelGGL((k_stem_pool2<f16_t, U8>), dim3(grid), dim3(NT), 0, st, a, tiles_w,
-                                   tiles_w * tiles_h, ntiles);
-            else
-                hipLaunchKernelGGL((k_stem_pool2<bf16_t, U8>), dim3(grid), dim3(NT), 0, st, a, tiles_w,
-                                   tiles_w * tiles_h, ntiles);
-        }
-        return;
-    }
-    constexpr int PH = 4, PW = 32;
-    const int tiles_w = (a.wp + PW - 1) / PW, tiles_h = (a.hp + PH - 1) / PH;
-    const int ntiles = a.n * tiles_h * tiles_w;
-    const int grid = ntiles < g_stem_cus ? ntiles : g_stem_cus;
-    if (dtype == RR_F16)
-        hipLaunchKernelGGL((k_stem_pool<PH, PW, f16_t, U8, TAB>), dim3(grid), dim3(NT), 0, st, a, rt, tiles_w,
-                           tiles_w * tiles_h, ntiles);
-    else
-        hipLaunchKernelGGL((k_stem_pool<PH, PW, bf16_t, U8, TAB>), dim3(grid), dim3(NT), 0, st, a, rt, tiles_w,
-                           tiles_w * tiles_h, ntiles);
+        run(k_stem_pool<4, 32, HT, U8, TAB>, 4, 32, rt);
+    };
+    if (dtype == RR_F16) pick(TypeTag<f16_t>{});
+    else pick(TypeTag<bf16_t>{});
 }
 
 // x: a same-size [n][3][h][w] batch, or (srcs != nullptr) a ragged batch whose
