@@ -46,6 +46,12 @@ class ConvDesc(ctypes.Structure):
                [("slope", ctypes.c_float), ("flags", ctypes.c_int)]
 
 
+class LaunchInfo(ctypes.Structure):
+    """rr_launch_info: what the last fused-conv entry on this thread launched."""
+    _fields_ = [("kernel", ctypes.c_char * 32), ("variant", ctypes.c_char * 48), ("grid", ctypes.c_uint),
+                ("block", ctypes.c_uint), ("nslices", ctypes.c_int), ("xmap", ctypes.c_int), ("launches", ctypes.c_int)]
+
+
 class Region(ctypes.Structure):
     """rr_region: one pooling rectangle of a stage map."""
     _fields_ = [(n, ctypes.c_uint16) for n in ("y0", "x0", "h", "w")]
@@ -159,6 +165,7 @@ _SIGS = {
     "rr_rank_full": ([_vp, _ll, _vp, _i, _i, _vp, _vp, _sz, _vp], _i),
     "rr_set_tuning": ([_i, _i], _i),
     "rr_get_tuning": ([_i, ctypes.POINTER(_i)], _i),
+    "rr_last_launch": ([ctypes.POINTER(LaunchInfo)], _i),
     "rr_fill_unit_rows": ([_vp, _ll, _i, ctypes.c_ulonglong, _ll, _vp], _i),
     "rr_cast_f32_bf16": ([_vp, _vp, _ll, _vp], _i),
     "rr_cast_f32_f16": ([_vp, _vp, _ll, _vp], _i),
@@ -218,6 +225,16 @@ def get_tuning(key):
 
 def set_tuning(key, value):
     check(lib().rr_set_tuning(_tune_key(key), int(value)), "rr_set_tuning")
+
+
+def last_launch():
+    """rr_last_launch as a dict: kernel ('' when the conv ran on the tiled engine or the
+    8-phase GEMM), variant, grid, block, nslices, xmap, launches.  Raises if no fused conv
+    has run on this thread."""
+    info = LaunchInfo()
+    check(lib().rr_last_launch(ctypes.byref(info)), "rr_last_launch")
+    return {"kernel": info.kernel.decode(), "variant": info.variant.decode(), "grid": info.grid, "block": info.block,
+            "nslices": info.nslices, "xmap": info.xmap, "launches": info.launches}
 
 
 @contextlib.contextmanager

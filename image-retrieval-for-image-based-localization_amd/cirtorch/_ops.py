@@ -84,19 +84,30 @@ def conv2d_fused(x, w_packed, kh, kw, stride, pad, c_out, scale=None, shift=None
     return y
 
 
+def _pair_out(out, shape_y, shape_z, dtype, device):
+    """The (y, z) destinations of a pair op: new tensors, or the caller's out=(y, z) checked as
+    conv2d_fused checks its out."""
+    if out is None:
+        return torch.empty(shape_y, dtype=dtype, device=device), torch.empty(shape_z, dtype=dtype, device=device)
+    y, z = out
+    E.require_gpu(y, z)
+    assert tuple(y.shape) == shape_y and y.dtype == dtype and y.is_contiguous()
+    assert tuple(z.shape) == shape_z and z.dtype == dtype and z.is_contiguous()
+    return y, z
+
+
 def conv1x1_pair(x, w3, scale3, shift3, residual, leaky3, slope3, w1, scale1, shift1, c_out, leaky1, slope1,
-                 proj=None):
+                 proj=None, out=None):
     """Fused y = act3(conv1x1(x, w3)*scale3 + shift3 + shortcut); z = act1(conv1x1(y, w1)*scale1 + shift1)
     (conv3 of one bottleneck block + conv1 of the next, cirtorch/backbones/misc.py:166-203).
     shortcut = residual, or with residual=None and proj=(xp, wp, scalep, shiftp) the block's 1x1
     projection proj_bn(proj_conv(xp)) computed in the same pass (64 -> 256 boundaries only).
     x: [N, H, W, 64] or [N, H, W, 128] bf16 / fp16, PERM32-packed weights; returns
-    (y [N, H, W, 256 | 512], z [N, H, W, c_out])."""
+    (y [N, H, W, 256 | 512], z [N, H, W, c_out]).  out: optional contiguous (y, z) destinations."""
     E.require_gpu(x, w3, residual, w1)
     n, h, w, c = x.shape
     c_mid = w3.shape[0]
-    y = torch.empty((n, h, w, c_mid), dtype=x.dtype, device=x.device)
-    z = torch.empty((n, h, w, c_out), dtype=x.dtype, device=x.device)
+    y, z = _pair_out(out, (n, h, w, c_mid), (n, h, w, c_out), x.dtype, x.device)
     assert x.is_contiguous()
     if residual is not None:
         assert residual.shape == y.shape and residual.dtype == x.dtype and residual.is_contiguous()
@@ -115,7 +126,8 @@ def conv1x1_pair(x, w3, scale3, shift3, residual, leaky3, slope3, w1, scale1, sh
 
 
 def conv3x3_pair(t1, w33, scale2, shift2, leaky2, slope2, w3, scale3, shift3, residual, leaky3, slope3,
-                 w1, scale1, shift1, c_out, leaky1, slope1, proj=None, dynamic=None, conv1=None):
+                 w1, scale1, shift1, c_out, leaky1, slope1, proj=None, dynamic=None, conv1=None,
+                 out=None):
     """One whole bottleneck block of the 256-channel stage plus the next block's conv1 in one
     launch (cirtorch/backbones/misc.py:163-203): t2 = act2(conv3x3(t1, w33)*scale2 + shift2),
     y = act3(conv1x1(t2, w3)*scale3 + shift3 + shortcut), z = act1(conv1x1(y, w1)*scale1 + shift1);
@@ -125,13 +137,13 @@ def conv3x3_pair(t1, w33, scale2, shift2, leaky2, slope2, w3, scale3, shift3, re
     followed by conv1x1_pair.  dynamic (default: RR_C3PAIR_QUEUE != "0"): per-XCD tile counters
     (a zeroed 8-int array per launch) instead of the static tile walk — same results.
     conv1=(w0, scale0, shift0, leaky0, slope0) (projection form, the stage's first block): t1 is
-    the block input x (pass it as proj's xp too) and the block's conv1 runs in the launch."""
+    the block input x (pass it as proj's xp too) and the block's conv1 runs in the launch.
+    out: optional contiguous (y, z) destinations."""
     E.require_gpu(t1, w33, w3, residual, w1)
     n, h, w, c = t1.shape
     assert c == 64 and t1.is_contiguous() and tuple(w33.shape) == (64, 576) and tuple(w3.shape) == (256, 64)
     assert tuple(w1.shape) == (c_out, 256)
-    y = torch.empty((n, h, w, 256), dtype=t1.dtype, device=t1.device)
-    z = torch.empty((n, h, w, c_out), dtype=t1.dtype, device=t1.device)
+    y, z = _pair_out(out, (n, h, w, 256), (n, h, w, c_out), t1.dtype, t1.device)
     if residual is not None:
         assert residual.shape == y.shape and residual.dtype == t1.dtype and residual.is_contiguous()
         xp = wp = sp = hp = None

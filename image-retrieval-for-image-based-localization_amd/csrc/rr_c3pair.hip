@@ -639,5 +639,7 @@ extern "C" int rr_conv3x3_pair(const void* t1, int n, int h, int w, const void* 
     };
     if (dtype == RR_F16) go(f16_t{});
     else go(bf16_t{});
+    // xmap: both tile walks are XCD-contiguous
+    note_launch("k_c3pair", (unsigned)grid, 512, 0, 1, 1, "%d%s%s", c_out, proj ? ",proj" : "", conv1 ? ",conv1" : "");
     return check_launch("rr_conv3x3_pair");
 }

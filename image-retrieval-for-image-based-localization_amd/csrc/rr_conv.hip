@@ -332,6 +332,7 @@ static bool use_v2(const ConvArgs& a, int dtype) {
 
 template <typename T, typename TO>
 static int dispatch(const ConvArgs& a, bool k1, int dtype, hipStream_t s) {
+    clear_launch();  // the tiled engine and the 8-phase GEMM leave the record empty
     if constexpr (sizeof(T) == 2 && std::is_same<T, TO>::value) {  // bf16 / fp16 fused kernels
         constexpr bool f16 = std::is_same<T, f16_t>::value;
         if (k1 && launch_stream1x1(a, s, f16)) return RR_OK;

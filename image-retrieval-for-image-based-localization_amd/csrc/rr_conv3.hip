@@ -632,6 +632,8 @@ void launch_c3(const ConvArgs& a, hipStream_t s, bool f16) {
     else
         hipLaunchKernelGGL((k_conv3x3<TC, TH, TW, WC, WP, ARES, NSA, bf16_t>), dim3(grid), dim3(64 * WC * WP), 0, s, a,
                            tiles_w, tiles_w * tiles_h, tiles_c, (int)ntl, pipe);
+    note_launch("k_conv3x3", (unsigned)grid, 64 * WC * WP, tiles_c, 0, 1, "%d,%d,%d,%d,%d,%d,pipe%d", TC, TH, TW, WC, WP,
+                NSA, pipe);
 }
 
 }  // namespace
@@ -664,6 +666,7 @@ bool launch_conv3x3(const ConvArgs& a, hipStream_t s, bool f16) {
         if (grid < 8) grid = 8;
         if (f16) hipLaunchKernelGGL(k_c3w64<f16_t>, dim3(grid), dim3(512), 0, s, a, tiles_w, tiles_hw, (int)ntl);
         else hipLaunchKernelGGL(k_c3w64<bf16_t>, dim3(grid), dim3(512), 0, s, a, tiles_w, tiles_hw, (int)ntl);
+        note_launch("k_c3w64", (unsigned)grid, 512, 0, 1, 1, "64,8,32");  // the XCD-contiguous walk: always on
         return true;
     }
     if (a.cin == 64 && a.cout == 64 && a.h % 8 == 0) {

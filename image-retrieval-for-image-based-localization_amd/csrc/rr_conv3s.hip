@@ -550,6 +550,7 @@ bool launch_conv3s(const ConvArgs& a, hipStream_t s, bool f16) {
         if (f16) hipLaunchKernelGGL((k_c3s_w128<f16_t>), g, b, 0, s, a, tiles_w, tiles_hw, (int)ntl);
         else hipLaunchKernelGGL((k_c3s_w128<bf16_t>), g, b, 0, s, a, tiles_w, tiles_hw, (int)ntl);
     }
+    note_launch(w64 ? "k_c3s_w64" : "k_c3s_w128", (unsigned)cus, 512, 0, 1, 1, "%s", "");
     return true;
 }
 

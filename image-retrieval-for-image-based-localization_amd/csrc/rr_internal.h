@@ -42,6 +42,12 @@ struct NoTab {};  // a same-size batch: one [n][c][H][W] buffer
 // returns an error message or nullptr.
 const char* ragged_fill(RaggedTab& t, const void* const* srcs, const int* extents, int i0, int cnt, int h, int w);
 
+// rr_last_launch's record (rr_runtime.hip): cleared by the conv dispatch, written by the
+// persistent kernels' launch sites.  variant is a printf format.
+void clear_launch();
+void note_launch(const char* kernel, unsigned grid, unsigned block, int nslices, int xmap, int launches,
+                 const char* variant, ...) __attribute__((format(printf, 7, 8)));
+
 // Launch-error check: every entry point ends with this.
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();

@@ -3,6 +3,8 @@
 // synthetic-row generator, f32->bf16 cast.  gfx950 only.
 #include "rr_internal.h"
 
+#include <cstdarg>
+#include <cstdio>
 #include <cstring>
 
 namespace rr {
@@ -58,6 +60,27 @@ void set_error(const std::string& msg) { g_err = msg; }
 int fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
+}
+
+static thread_local rr_launch_info g_launch;
+static thread_local bool g_launch_set = false;
+
+void clear_launch() {
+    std::memset(&g_launch, 0, sizeof g_launch);
+    g_launch_set = true;
+}
+void note_launch(const char* kernel, unsigned grid, unsigned block, int nslices, int xmap, int launches,
+                 const char* variant, ...) {
+    rr_launch_info r;
+    std::memset(&r, 0, sizeof r);
+    std::snprintf(r.kernel, sizeof r.kernel, "%s", kernel);
+    va_list ap;
+    va_start(ap, variant);
+    std::vsnprintf(r.variant, sizeof r.variant, variant, ap);
+    va_end(ap);
+    r.grid = grid; r.block = block; r.nslices = nslices; r.xmap = xmap; r.launches = launches;
+    g_launch = r;
+    g_launch_set = true;
 }
 
 // ------------------------------------------------------------------ normalise
@@ -452,6 +475,13 @@ int rr_get_tuning(int key, int* value) {
     if (key < 0 || key >= TUNE_NKEYS) return fail(RR_EINVAL, "rr_get_tuning: unknown key");
     if (!value) return fail(RR_EINVAL, "rr_get_tuning: null value");
     *value = g_tune.*TUNE_KEYS[key].member;
+    return RR_OK;
+}
+
+int rr_last_launch(rr_launch_info* out) {
+    if (!out) return fail(RR_EINVAL, "rr_last_launch: null out");
+    if (!g_launch_set) return fail(RR_EINVAL, "rr_last_launch: nothing recorded on this thread");
+    *out = g_launch;
     return RR_OK;
 }
 

@@ -1086,6 +1086,8 @@ void launch_s_t(const ConvArgs& a, hipStream_t s) {
         hipLaunchKernelGGL((k_stream1x1<TC, K, FN, D, NW, true, H>), dim3(grid), dim3(64 * NW), 0, s, a, nslices, xmap);
     else
         hipLaunchKernelGGL((k_stream1x1<TC, K, FN, D, NW, false, H>), dim3(grid), dim3(64 * NW), 0, s, a, nslices, xmap);
+    note_launch("k_stream1x1", grid, 64 * NW, nslices, xmap, 1, "%d,%d,%d,%d,%d%s", TC, K, FN, D, NW,
+                (a.flags & RR_CONV_RESIDUAL) ? ",res" : "");
 }
 
 template <int K, int CW>
@@ -1109,6 +1111,7 @@ void launch_wres(const ConvArgs& a, hipStream_t s, bool f16) {
     long long ich = (1ll << 31) / (in_img > out_img ? in_img : out_img);
     if (ich < 1) ich = 1;
     const long long hw = (long long)a.ho * a.wo;
+    int launches = 0;
     for (long long i0 = 0; i0 < a.n; i0 += ich) {
         const long long ni = a.n - i0 < ich ? a.n - i0 : ich;
         w.x = (const bf16_t*)a.x + i0 * a.h * a.w_ * K;
@@ -1127,6 +1130,8 @@ void launch_wres(const ConvArgs& a, hipStream_t s, bool f16) {
         };
         if (f16) go(f16_t{});
         else go(bf16_t{});
+        note_launch("k_wres1x1", grid, 512, w.nslices, w.xmap, ++launches, "%d,%d,%s", K, CW,
+                    res ? "res" : (g_tune.wres_ring ? "ring" : "noring"));
     }
 }
 }  // namespace
@@ -1220,6 +1225,7 @@ extern "C" int rr_conv1x1_pair(const void* x, long long p, int c_in, const void*
     if (stage3) {
         // pixel chunks of 2^20 (the residual buffer resource addresses 1 GiB with 32-bit offsets)
         constexpr long long CH = 1ll << 20;
+        int launches = 0;
         for (long long p0 = 0; p0 < p; p0 += CH) {
             PairMidArgs m;
             const long long pn = p - p0 < CH ? p - p0 : CH;
@@ -1236,6 +1242,7 @@ extern "C" int rr_conv1x1_pair(const void* x, long long p, int c_in, const void*
                 if (dtype == RR_F16) hipLaunchKernelGGL(k_pair_mid<f16_t>, dim3(grid), dim3(512), 0, s, m);
                 else hipLaunchKernelGGL(k_pair_mid<bf16_t>, dim3(grid), dim3(512), 0, s, m);
             }
+            note_launch(g_tune.pair_mid ? "k_pair_mid_ring" : "k_pair_mid", grid, 512, 0, 0, ++launches, "128,512,128,res");
         }
         return check_launch("rr_conv1x1_pair");
     }
@@ -1257,5 +1264,6 @@ extern "C" int rr_conv1x1_pair(const void* x, long long p, int c_in, const void*
     };
     if (dtype == RR_F16) go(f16_t{});
     else go(bf16_t{});
+    note_launch("k_stream_pair", (unsigned)grid, 512, 0, 0, 1, "%d,2,%s", c_out, proj ? "proj" : "res");
     return check_launch("rr_conv1x1_pair");
 }

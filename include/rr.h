@@ -1264,6 +1264,18 @@ enum rr_tune_size_key { RR_TUNE_SIZE_BASE = 32, RR_TUNE_PATCHNET_CHUNK = 32 };
 int rr_set_tuning(int key, int value);
 int rr_get_tuning(int key, int* value);
 
+/* What the last fused-conv entry on this thread launched (for tests: the kernel a shape
+ * dispatches to and its persistent grid are otherwise arithmetic nobody can observe).
+ * Host-only and thread-local: one struct copy per launch, nothing on the device.
+ * rr_conv2d_fused clears the record on entry, so a conv that runs on the tiled engine or the
+ * 8-phase GEMM reads back with an empty kernel; the persistent kernels (k_wres1x1,
+ * k_stream1x1, k_stream_pair, k_pair_mid, k_pair_mid_ring, k_c3pair, k_conv3x3, k_c3w64,
+ * k_c3s) record their name, template variant, grid and block size, output-channel slices
+ * (0 where the kernel has none), whether the XCD tile map is on, and how many launches
+ * (image or pixel chunks) the entry made.  RR_EINVAL if nothing was recorded on this thread. */
+typedef struct { char kernel[32]; char variant[48]; unsigned grid, block; int nslices, xmap, launches; } rr_launch_info;
+int rr_last_launch(rr_launch_info* out);
+
 /* ----------------------------------------------------------- data helpers */
 /* Counter-based N(0,1) rows, each L2-normalised: row i of the global matrix
  * depends only on (seed, i0 + i), so shards generate identical rows. */

@@ -335,3 +335,42 @@ def test_apply_tuning_arg_takes_names_and_numbers():
     finally:
         for key, value in start.items():
             E.set_tuning(key, value)
+
+
+def test_launch_info_layout_matches_header():
+    from cirtorch import _engine as E
+    text = open(HEADER).read()
+    body = re.search(r"typedef struct \{(.*?)\} rr_launch_info;", text, re.S).group(1)
+    fields = []
+    for decl in filter(None, (d.strip() for d in body.split(";"))):
+        typ, names = decl.rsplit(None, 1) if "," not in decl else decl.split(None, 1)
+        if typ == "char":
+            name, size = re.fullmatch(r"(\w+)\[(\d+)\]", names).groups()
+            fields.append((name, ctypes.c_char * int(size)))
+        else:
+            fields += [(n.strip(), {"unsigned": ctypes.c_uint, "int": ctypes.c_int}[typ]) for n in names.split(",")]
+    assert fields == list(E.LaunchInfo._fields_)
+    assert ctypes.sizeof(E.LaunchInfo) == 32 + 48 + 5 * 4
+
+
+def test_last_launch_is_thread_local_and_checks_its_argument():
+    """Nothing has been recorded on a new thread (RR_EINVAL, the message names the function); a null pointer
+    is refused; neither call needs a device."""
+    import threading
+    from cirtorch import _engine as E
+    lib, seen = E.lib(), {}
+
+    def fresh():
+        info = E.LaunchInfo()
+        seen["rc"] = lib.rr_last_launch(ctypes.byref(info))
+        seen["err"] = lib.rr_last_error()
+        try:
+            E.last_launch()
+        except RuntimeError as e:
+            seen["raised"] = str(e)
+
+    t = threading.Thread(target=fresh)
+    t.start()
+    t.join()
+    assert seen["rc"] == -1 and b"rr_last_launch" in seen["err"] and "rr_last_launch" in seen["raised"]
+    assert lib.rr_last_launch(None) == -1 and b"rr_last_launch: null" in lib.rr_last_error()
