@@ -26,6 +26,8 @@
 // (CONV1, the stage's first block): the block's own conv1 (1x1 64 -> 64) applied to the patch
 // in LDS, so the launch reads the block input instead of t1.
 #include "rr_internal.h"
+#include "rr_ldsdma.h"
+#include "rr_tilewalk.h"
 
 #ifndef C3P_IG2
 #define C3P_IG2 1
@@ -35,45 +37,6 @@ namespace rr {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float cf32x4_t;
-typedef __attribute__((ext_vector_type(4))) int ci32x4_t;
-
-constexpr unsigned COOB = 0x80000000u;  // voffset beyond every buffer: the DMA writes zeros
-
-__device__ __forceinline__ void cdma16(ci32x4_t rsrc, unsigned voff, unsigned lds_addr) {
-    unsigned keep;
-    lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 0\n\t"  // M0 write -> LDS-DMA: 1 wait state (descriptor: fenced in the rsrc maker)
-        "buffer_load_dwordx4 %1, %2, 0 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(rsrc), "s"(lds_addr)
-        : "memory");
-}
-
-__device__ __forceinline__ ci32x4_t crsrc(const void* base, unsigned bytes) {
-    const unsigned long long b = (unsigned long long)base;
-    ci32x4_t r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)b);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(b >> 32) & 0xFFFFu));
-    r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-    r.w = 0x00020000;
-    // VALU (readfirstlane) SGPR write -> LDS-DMA descriptor read: 5 wait states, tied to the
-    // registers so no use of the descriptor is scheduled above it (tools/dma_audit.py checks)
-    int x = r.x, y = r.y, z = r.z;
-    asm volatile("s_nop 4" : "+s"(x), "+s"(y), "+s"(z));
-    r.x = x;
-    r.y = y;
-    r.z = z;
-    return r;
-}
-
-// t2 reaches the LDS by ds_write (not DMA): its writes must be done before the barrier
-__device__ __forceinline__ void cbar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // k_stream_pair's weight image swizzle (every ds_read_b128 lane group of an A fragment hits
 // 16 distinct 4-bank groups)
 template <int K>
@@ -81,8 +44,6 @@ __device__ __forceinline__ int cwswz(int row, int chunk) {
     const int f = K == 64 ? ((row >> 1) & 7) : (row & 15);
     return row * (K * 2) + ((chunk ^ f) << 4);
 }
-
-__device__ __forceinline__ void cpin(uint4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
 
 }  // namespace
 
@@ -177,22 +138,20 @@ __global__ void __launch_bounds__(512, 1) k_c3pair(C3PairArgs a, int tiles_w, in
         }
     const int wc = wave & 1, wpx = (wave >> 1) & 1;  // 3x3 role: channel half, pixel half
 
-    // ---- this block's tiles.  Static: k_c3w64's XCD-contiguous walk.  Dynamic (a.queue):
+    // ---- this block's tiles (rr_tilewalk.h).  Static: the round walk.  Dynamic (a.queue):
     // XCD x = blockIdx & 7 owns the contiguous tile range [s_x, s_x + n_x) and its blocks take
     // the next tile from the XCD's counter, so a block that starts late (its CU still held by
     // another stream's kernel) takes fewer tiles instead of finishing its fixed share late.
     // Thread 0 fetches step s's tile during step s - 3 into sTile (both roles read it after
     // the barriers that follow).
-    const int b = (int)blockIdx.x, G = (int)gridDim.x, xcd = b & 7;
-    const int nt8 = ntiles >> 3, rt8 = ntiles & 7;
-    const int s_x = xcd < rt8 ? xcd * (nt8 + 1) : rt8 * (nt8 + 1) + (xcd - rt8) * nt8;
-    const int n_x = nt8 + (xcd < rt8 ? 1 : 0);
+    const int b = (int)blockIdx.x, G = (int)gridDim.x;
+    const XcdTiles tr = xcd_tiles(b, ntiles);
     auto fetch_tile = [&](int i) __attribute__((always_inline)) {
         if (a.queue) {
-            const int v = atomicAdd(a.queue + xcd, 1);
-            return v < n_x ? s_x + v : -1;
+            const int v = atomicAdd(a.queue + (b & 7), 1);
+            return v < tr.n_x ? tr.s_x + v : -1;
         }
-        const int t = i * G + xcd * (G >> 3) + (b >> 3);
+        const int t = xcd_round_tile(b, G, i);
         return t < ntiles ? t : -1;
     };
     if (tid == 0) {
@@ -211,7 +170,7 @@ __global__ void __launch_bounds__(512, 1) k_c3pair(C3PairArgs a, int tiles_w, in
     };
 
     // ================================================================= 3x3 role state
-    const ci32x4_t rsX = crsrc(a.t1, (unsigned)((long long)a.n * H * W * 64 * 2));
+    const i32x4_t rsX = make_rsrc(a.t1, (unsigned)((long long)a.n * H * W * 64 * 2));
     const unsigned ldsP = (unsigned)(unsigned long long)sPatch;
     // patch pieces d = wave + 4 u (30 per patch: waves 0-1 issue 8, waves 2-3 issue 7)
     auto patch_dma = [&](int t, bool live) __attribute__((always_inline)) {
@@ -228,13 +187,13 @@ __global__ void __launch_bounds__(512, 1) k_c3pair(C3PairArgs a, int tiles_w, in
             if (d >= NP) break;  // wave-uniform
             const int pr = q / PITCH, pc = q - pr * PITCH;
             const int hh = oh0 - 1 + pr, ww = ow0 - 1 + pc;
-            unsigned off = COOB;
+            unsigned off = OOB;
             if (live && pc < PCW && (unsigned)hh < (unsigned)H && (unsigned)ww < (unsigned)W)
                 off = (unsigned)(((((long long)img * H + hh) * W + ww) * 64 + ((lch ^ lr) << 3)) * 2);
-            cdma16(rsX, off, ldsP + d * 1024);
+            dma16(rsX, off, ldsP + d * 1024);
         }
     };
-    h16_f32x4_t acc[2][FN];
+    f32x4_t acc[2][FN];
     // the tile's 3x3 (k_c3w64's K-step loop: 18 x (4 fragment reads, 8 MFMAs))
     auto conv3x3 = [&](const uint4 (&areg)[2][18]) __attribute__((always_inline)) {
         // fragment address bases (pixel fragment j, tap column dx, half-step hs), derived per
@@ -256,7 +215,7 @@ __global__ void __launch_bounds__(512, 1) k_c3pair(C3PairArgs a, int tiles_w, in
 #pragma unroll
         for (int ii = 0; ii < 2; ++ii)
 #pragma unroll
-            for (int j = 0; j < FN; ++j) acc[ii][j] = (h16_f32x4_t){0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < FN; ++j) acc[ii][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < 18; ++s) {
             const int tap = s >> 1, hs = s & 1, dy = tap / 3, dx = tap % 3;
@@ -289,9 +248,9 @@ __global__ void __launch_bounds__(512, 1) k_c3pair(C3PairArgs a, int tiles_w, in
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk)
                     bx[kk] = *reinterpret_cast<const uint4*>(slot + (((4 * kk + kq) ^ (q & 7)) << 4));
-                h16_f32x4_t c0[4];
+                f32x4_t c0[4];
 #pragma unroll
-                for (int ii = 0; ii < 4; ++ii) c0[ii] = (h16_f32x4_t){0.f, 0.f, 0.f, 0.f};
+                for (int ii = 0; ii < 4; ++ii) c0[ii] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
@@ -394,11 +353,11 @@ __global__ void __launch_bounds__(512, 1) k_c3pair(C3PairArgs a, int tiles_w, in
         for (int i0 = 0; i0 < NR3; i0 += IG) {
             int abase = 0;
             asm volatile("" : "+v"(abase));  // keep the weight fragments in LDS (no hoisting into VGPRs)
-            h16_f32x4_t acc3[IG][2], pacc[IG][2];
+            f32x4_t acc3[IG][2], pacc[IG][2];
 #pragma unroll
             for (int g = 0; g < IG; ++g)
 #pragma unroll
-                for (int hh = 0; hh < 2; ++hh) acc3[g][hh] = pacc[g][hh] = (h16_f32x4_t){0.f, 0.f, 0.f, 0.f};
+                for (int hh = 0; hh < 2; ++hh) acc3[g][hh] = pacc[g][hh] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kk = 0; kk < NK3; ++kk)
 #pragma unroll
@@ -455,9 +414,9 @@ __global__ void __launch_bounds__(512, 1) k_c3pair(C3PairArgs a, int tiles_w, in
                 st16_once(a.y + p * C3 + c, yq[i2]);
             }
         }
-        h16_f32x4_t zacc[NF1];
+        f32x4_t zacc[NF1];
 #pragma unroll
-        for (int o = 0; o < NF1; ++o) zacc[o] = (h16_f32x4_t){0.f, 0.f, 0.f, 0.f};
+        for (int o = 0; o < NF1; ++o) zacc[o] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kk = 0; kk < NK1; ++kk) {
             int abase = 0;
@@ -505,32 +464,32 @@ __global__ void __launch_bounds__(512, 1) k_c3pair(C3PairArgs a, int tiles_w, in
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int ks = 0; ks < 18; ++ks) cpin(areg[i][ks]);
+            for (int ks = 0; ks < 18; ++ks) pin_loaded(areg[i][ks]);
         auto conv = [&]() __attribute__((always_inline)) { conv3x3(areg); };
         // prologue: tile 0's 3x3 (strips 0-3 stored now, 4-7 at the start of step 0), tile 1's patch
         patch_dma(tile_id(0), true);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        cbar();
+        vm_wait<0>();
+        lds_barrier();
         if constexpr (CONV1) {
             convert_patch(tile_id(0));
-            cbar();
+            lds_barrier();
         }
         conv();
         if (wpx == 0) store_t2();
-        cbar();  // every 3x3 wave is done with patch 0
+        lds_barrier();  // every 3x3 wave is done with patch 0
         patch_dma(tile_id(1), tile_id(1) >= 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        cbar();
+        vm_wait<0>();
+        lds_barrier();
         for (int s = 0; tile_id(s) >= 0; ++s) {
             const bool more = tile_id(s + 1) >= 0;
             // phase A: tile s's strips 4-7 (lower pixel half), then tile s + 1's 3x3
             if (wpx == 1) store_t2();
             if constexpr (CONV1) {
                 if (more) convert_patch(tile_id(s + 1));
-                cbar();
+                lds_barrier();
             }
             if (more) conv();
-            cbar();
+            lds_barrier();
             // phase B: tile s + 1's strips 0-3 (upper pixel half), tile s + 2's patch
             if (more) {
                 if (wpx == 0) store_t2();
@@ -538,9 +497,9 @@ __global__ void __launch_bounds__(512, 1) k_c3pair(C3PairArgs a, int tiles_w, in
                 patch_dma(t2i, t2i >= 0);
                 // step s + 3's tile into the slot step s - 1 used (read by no one after step s - 1)
                 if (tid == 0) sTile[(s + 3) & 3] = t2i >= 0 ? fetch_tile(s + 3) : -1;
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                vm_wait<0>();
             }
-            cbar();
+            lds_barrier();
         }
     } else {
         // the HBM stream issues ahead of the 3x3 role's MFMA run on the same SIMD
@@ -551,32 +510,32 @@ __global__ void __launch_bounds__(512, 1) k_c3pair(C3PairArgs a, int tiles_w, in
         uint4 rq[4][NRQ];
         load_rq(rq[0], strip_pixel(tile_id(0), pw));
         load_rq(rq[1], strip_pixel(tile_id(0), 4 + pw));
-        cbar();
-        if constexpr (CONV1) cbar();  // the 3x3 role's conv1 of patch 0
-        cbar();
-        cbar();
+        lds_barrier();
+        if constexpr (CONV1) lds_barrier();  // the 3x3 role's conv1 of patch 0
+        lds_barrier();
+        lds_barrier();
         for (int s = 0; tile_id(s) >= 0; s += 2) {
             {  // tile s from buffers 0 / 1, tile s + 1's into 2 / 3
                 const int t = tile_id(s);
                 const bool n1 = tile_id(s + 1) >= 0;
                 if (n1) load_rq(rq[2], strip_pixel(tile_id(s + 1), pw));
-                if constexpr (CONV1) cbar();  // the 3x3 role's conv1 of the next patch
+                if constexpr (CONV1) lds_barrier();  // the 3x3 role's conv1 of the next patch
                 pair_strip(pw, strip_pixel(t, pw), rq[0]);
-                cbar();
+                lds_barrier();
                 if (n1) load_rq(rq[3], strip_pixel(tile_id(s + 1), 4 + pw));
                 pair_strip(4 + pw, strip_pixel(t, 4 + pw), rq[1]);
-                cbar();
+                lds_barrier();
             }
             if (tile_id(s + 1) >= 0) {  // tile s + 1 from buffers 2 / 3, tile s + 2's into 0 / 1
                 const int t = tile_id(s + 1);
                 const bool n2 = tile_id(s + 2) >= 0;
                 if (n2) load_rq(rq[0], strip_pixel(tile_id(s + 2), pw));
-                if constexpr (CONV1) cbar();
+                if constexpr (CONV1) lds_barrier();
                 pair_strip(pw, strip_pixel(t, pw), rq[2]);
-                cbar();
+                lds_barrier();
                 if (n2) load_rq(rq[1], strip_pixel(tile_id(s + 2), 4 + pw));
                 pair_strip(4 + pw, strip_pixel(t, 4 + pw), rq[3]);
-                cbar();
+                lds_barrier();
             }
         }
     }
@@ -626,8 +585,7 @@ extern "C" int rr_conv3x3_pair(const void* t1, int n, int h, int w, const void* 
     const long long ntl = (long long)n * tiles_hw;
     if (ntl >= (1ll << 31)) return fail(RR_EINVAL, "rr_conv3x3_pair: too many tiles");
     const int cus = grid_cus();
-    int grid = (int)(ntl < cus ? ntl : cus) & ~7;
-    if (grid < 8) grid = 8;
+    const int grid = persistent_grid8(ntl, cus);
     const dim3 g((unsigned)grid), b(512);
     hipStream_t s = as_stream(stream);
     auto go = [&](auto hv) {

@@ -23,44 +23,17 @@
 // + residual add/activation (backbones/misc.py:184-203); also the score GEMM
 // of the kNN (scripts/test.py:247).
 #include "rr_internal.h"
+#include "rr_ldsdma.h"
 
 #include <cstdlib>
 
 namespace rr {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-
-template <typename T> struct Vec;
-template <> struct Vec<bf16_t> { static constexpr int N = 8; };
-template <> struct Vec<float> { static constexpr int N = 4; };
 
 __device__ __forceinline__ int lds_off(int row, int chunk) {
     return row * 64 + ((chunk ^ (((row >> 3) & 1) * 3)) << 4);
 }
-
-template <typename TO> struct Store4;
-template <> struct Store4<float> {
-    static __device__ __forceinline__ void st(float* p, const float* v) {
-        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-    static __device__ __forceinline__ void ld(const float* p, float* v) {
-        float4 t = *reinterpret_cast<const float4*>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    }
-};
-template <> struct Store4<bf16_t> {
-    static __device__ __forceinline__ void st(bf16_t* p, const float* v) {
-        ushort4 o;
-        o.x = f2bf(v[0]); o.y = f2bf(v[1]); o.z = f2bf(v[2]); o.w = f2bf(v[3]);
-        *reinterpret_cast<ushort4*>(p) = o;
-    }
-    static __device__ __forceinline__ void ld(const bf16_t* p, float* v) {
-        ushort4 t = *reinterpret_cast<const ushort4*>(p);
-        v[0] = bf2f(t.x); v[1] = bf2f(t.y); v[2] = bf2f(t.z); v[3] = bf2f(t.w);
-    }
-};
 
 template <typename T, typename TO, int TC, int TP, int WC, int WP, bool K1>
 __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
@@ -150,11 +123,11 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
             if (b_in[i]) *reinterpret_cast<uint4*>(Bs + b_off[i]) = rb[i];
     };
 
-    f32x4 acc[FM][FN];
+    f32x4_t acc[FM][FN];
 #pragma unroll
     for (int i = 0; i < FM; ++i)
 #pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
     const int nk = a.kp / BK;
     const int r16 = lane & 15, kq = lane >> 4;
@@ -235,8 +208,8 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
         const bool full = (c + 3 < a.cout);
         if (affine) {
             if (full) {
-                Store4<float>::ld(a.scale + c, sc);
-                Store4<float>::ld(a.shift + c, sh);
+                St4<float>::ld(a.scale + c, sc);
+                St4<float>::ld(a.shift + c, sh);
             } else {
                 for (int r = 0; r < 4; ++r)
                     if (c + r < a.cout) { sc[r] = a.scale[c + r]; sh[r] = a.shift[c + r]; }
@@ -253,7 +226,7 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
             if (full) {
                 if (resid) {
                     float rv[4];
-                    Store4<TO>::ld(R + o, rv);
+                    St4<TO>::ld(R + o, rv);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] += rv[r];
                 }
@@ -261,7 +234,7 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope;
                 }
-                Store4<TO>::st(Y + o, v);
+                St4<TO>::st(Y + o, v);
             } else {
                 for (int r = 0; r < 4; ++r) {
                     if (c + r >= a.cout) break;

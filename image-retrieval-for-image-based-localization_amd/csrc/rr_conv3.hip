@@ -27,65 +27,14 @@
 // 166-172, stride on this conv; here the stride-1 blocks) + the ABN eval BN +
 // leaky_relu (cirtorch/utils/misc.py:175-235).
 #include "rr_internal.h"
+#include "rr_ldsdma.h"
+#include "rr_tilewalk.h"
 
 #include <type_traits>
 
 namespace rr {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) float pf32x4_t;
-typedef __attribute__((ext_vector_type(4))) int pi32x4_t;
-
-constexpr unsigned POOB = 0x80000000u;  // voffset beyond every buffer: the DMA writes zeros
-
-// One 16-B-per-lane LDS-DMA wave-instruction: LDS[lds_addr + lane*16] = buf[voff].
-__device__ __forceinline__ void pdma16(pi32x4_t rsrc, unsigned voff, unsigned lds_addr) {
-    unsigned keep;
-    lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 0\n\t"  // M0 write -> LDS-DMA: 1 wait state (descriptor: fenced in the rsrc maker)
-        "buffer_load_dwordx4 %1, %2, 0 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(rsrc), "s"(lds_addr)
-        : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void pwait_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"i"(N) : "memory");
-}
-// vmcnt(n) + barrier for a wave-uniform runtime n <= N (a chain of scalar
-// compares picks the exact immediate).
-template <int N>
-__device__ __forceinline__ void pwait_barrier_n(int n) {
-    if constexpr (N == 0) {
-        pwait_barrier<0>();
-    } else {
-        if (n >= N) pwait_barrier<N>();
-        else pwait_barrier_n<N - 1>(n);
-    }
-}
-
-__device__ __forceinline__ pi32x4_t prsrc(const void* base, unsigned bytes) {
-    const unsigned long long b = (unsigned long long)base;
-    pi32x4_t r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)b);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(b >> 32) & 0xFFFFu));
-    r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-    r.w = 0x00020000;
-    // VALU (readfirstlane) SGPR write -> LDS-DMA descriptor read: 5 wait states, tied to the
-    // registers so no use of the descriptor is scheduled above it (tools/dma_audit.py checks)
-    int x = r.x, y = r.y, z = r.z;
-    asm volatile("s_nop 4" : "+s"(x), "+s"(y), "+s"(z));
-    r.x = x;
-    r.y = y;
-    r.z = z;
-    return r;
-}
 
 struct TileC {
     int ct, img, oh0, ow0;
@@ -118,7 +67,7 @@ __global__ void __launch_bounds__(64 * WC * WP) k_conv3x3(ConvArgs a, int tiles_
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wc = wave % WC, wp = wave / WC;
     const int H = a.h, W = a.w_, Cin = a.cin, nck = Cin >> 6;
-    const pi32x4_t rsX = prsrc(a.x, (unsigned)((long long)a.n * H * W * Cin * 2));
+    const i32x4_t rsX = make_rsrc(a.x, (unsigned)((long long)a.n * H * W * Cin * 2));
     const unsigned lds0 = (unsigned)(unsigned long long)smem;
     const int lrow = lane >> 3, lch = lane & 7;
 
@@ -152,19 +101,19 @@ __global__ void __launch_bounds__(64 * WC * WP) k_conv3x3(ConvArgs a, int tiles_
         const int q = d * 8 + lrow;
         const int pr = q / PC, pc = q - pr * PC;
         const int hh = tc.oh0 - 1 + pr, ww = tc.ow0 - 1 + pc;
-        unsigned off = POOB;
+        unsigned off = OOB;
         if (q < NPIX && (unsigned)hh < (unsigned)H && (unsigned)ww < (unsigned)W)
             off = (unsigned)(((((long long)tc.img * H + hh) * W + ww) * Cin + cc * 64 + ((lch ^ lrow) << 3)) * 2);
-        pdma16(rsX, off, lds0 + ABYTES + buf * PBYTES + d * 1024);
+        dma16(rsX, off, lds0 + ABYTES + buf * PBYTES + d * 1024);
     };
     // weight K-step (tap, chunk cc) of channel tile ct -> LDS dst ([TC rows][128 B], swizzled)
     auto w_dma = [&](int ct, int tap, int cc, unsigned dst) {
-        const pi32x4_t rsW = prsrc((const char*)a.w + (long long)ct * TC * a.kp * 2, (unsigned)(TC * a.kp * 2));
+        const i32x4_t rsW = make_rsrc((const char*)a.w + (long long)ct * TC * a.kp * 2, (unsigned)(TC * a.kp * 2));
         const unsigned k0b = (unsigned)((tap * Cin + cc * 64) * 2);
 #pragma unroll
         for (int i = 0; i < NIA; ++i) {
             const int row = (wave + NW * i) * 8 + lrow;
-            pdma16(rsW, (unsigned)(row * a.kp * 2) + k0b + (unsigned)((lch ^ lrow) << 4), dst + (wave + NW * i) * 1024);
+            dma16(rsW, (unsigned)(row * a.kp * 2) + k0b + (unsigned)((lch ^ lrow) << 4), dst + (wave + NW * i) * 1024);
         }
     };
 
@@ -177,11 +126,11 @@ __global__ void __launch_bounds__(64 * WC * WP) k_conv3x3(ConvArgs a, int tiles_
         bq[j] = (p / TW) * PC + (p % TW) + r16;
     }
 
-    pf32x4_t acc[FM][FN];
+    f32x4_t acc[FM][FN];
 #pragma unroll
     for (int i = 0; i < FM; ++i)
 #pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = (pf32x4_t){0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
     // A / B fragments of half-step hs (channels 32*hs .. +31 of the 64-channel
     // K-step) at tap offset toff, and the FM x FN MFMAs on them
@@ -218,7 +167,7 @@ __global__ void __launch_bounds__(64 * WC * WP) k_conv3x3(ConvArgs a, int tiles_
     // output channels of one pixel -> one 16-B store; exactly NST stores.
     // one 16-B store of the epilogue: fragment pair (2*i2, 2*i2+1) x pixel
     // fragment j of accumulators `ac`, BN affine (sc, sh: this lane's 8 channels)
-    auto store_one = [&](const TileC& tc, const pf32x4_t (&ac)[FM][FN], int i2, int j, const float (&sc)[8],
+    auto store_one = [&](const TileC& tc, const f32x4_t (&ac)[FM][FN], int i2, int j, const float (&sc)[8],
                          const float (&sh)[8]) {
         const int c = tc.ct * TC + wc * (TC / WC) + 32 * i2 + 8 * kq;
         const int p = wp * (TP / WP) + j * 16 + r16;
@@ -262,7 +211,7 @@ __global__ void __launch_bounds__(64 * WC * WP) k_conv3x3(ConvArgs a, int tiles_
 #pragma unroll
         for (int i = 0; i < FM; ++i)
 #pragma unroll
-            for (int j = 0; j < FN; ++j) acc[i][j] = (pf32x4_t){0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
     };
 
     TileC cur = tile_of(0);
@@ -280,7 +229,7 @@ __global__ void __launch_bounds__(64 * WC * WP) k_conv3x3(ConvArgs a, int tiles_
             // (all waves reach the epilogue together: one barrier per tile).
             // Branch-free activation: leaky(v) = max(v, slope * v) for slope in
             // [0, 1] (host-checked; identity = slope 1), bit-equal to the select form.
-            pf32x4_t accP[FM][FN];
+            f32x4_t accP[FM][FN];
             float esc[FM / 2][8], esh[FM / 2][8];  // one channel tile: the affine stays in VGPRs
             const float sl = leaky ? slope : 1.f;
             auto store_bf = [&](const TileC& tc, int i2, int j) {
@@ -341,14 +290,14 @@ __global__ void __launch_bounds__(64 * WC * WP) k_conv3x3(ConvArgs a, int tiles_
 #pragma unroll
                     for (int j = 0; j < FN; ++j) {
                         accP[i][j] = acc[i][j];
-                        acc[i][j] = (pf32x4_t){0.f, 0.f, 0.f, 0.f};
+                        acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
                     }
             };
             for (int lt = 0; lt < my_tiles; ++lt) {
                 // patch(lt) landed; from lt = 2 on the NST stores of tile lt - 2 (issued
                 // during tile lt - 1, after patch(lt)'s DMA) may stay in flight
-                if (lt <= 1) pwait_barrier<0>();
-                else pwait_barrier<NST>();
+                if (lt <= 1) vm_wait_barrier<0>();
+                else vm_wait_barrier<NST>();
                 if (lt == 0) {
 #pragma unroll
                     for (int i2 = 0; i2 < FM / 2; ++i2) load_affine(0, i2, esc[i2], esh[i2]);
@@ -367,8 +316,8 @@ __global__ void __launch_bounds__(64 * WC * WP) k_conv3x3(ConvArgs a, int tiles_
         } else {
             for (int lt = 0; lt < my_tiles; ++lt) {
                 // patch(lt) landed (older than the previous tile's NST epilogue stores)
-                if (lt == 0) pwait_barrier<0>();
-                else pwait_barrier<NST>();
+                if (lt == 0) vm_wait_barrier<0>();
+                else vm_wait_barrier<NST>();
                 if (lt + 1 < my_tiles) {
                     const TileC nxt = tile_of(lt + 1);
                     for (int d = wave; d < NDP; d += NW) patch_dma(nxt, 0, (lt + 1) & 1, d);
@@ -402,9 +351,9 @@ __global__ void __launch_bounds__(64 * WC * WP) k_conv3x3(ConvArgs a, int tiles_
         for (int s = 0; s < total; ++s) {
             // A(s) landed; only the younger VMEM ops (later weight steps, patch
             // pieces, the previous tile's epilogue stores) may stay in flight
-            if (s == 0) pwait_barrier<0>();
-            else if constexpr (NSA == 2) pwait_barrier_n<NST + 1>(tm1);
-            else pwait_barrier_n<NIA + NST + 2>(tm2 + am1 + tm1);
+            if (s == 0) vm_wait_barrier<0>();
+            else if constexpr (NSA == 2) vm_wait_barrier_n<NST + 1>(tm1);
+            else vm_wait_barrier_n<NIA + NST + 2>(tm2 + am1 + tm1);
             int ntap = tap, ncc = cc, nlt = lt;
             adv(ntap, ncc, nlt);
             int a_now = 0, t_now = 0;
@@ -462,14 +411,6 @@ __global__ void __launch_bounds__(64 * WC * WP) k_conv3x3(ConvArgs a, int tiles_
 // tiles walked XCD-contiguously (the 32 tiles an XCD holds at once are 4 tile
 // rows of one image: vertical halo re-reads hit its L2).  Accumulation order
 // (tap, half-step) equals k_conv3x3's: bit-identical outputs.
-// A value loaded once before a loop (weights kept in VGPRs): passing it through an
-// empty asm makes the asm its producer, so the compiler's wait for the load sits
-// before the loop instead of (counted against the loop's own LDS-DMA / stores,
-// which it cannot see) in front of every use inside it.
-__device__ __forceinline__ void pin_loaded(uint4& v) {
-    asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w));
-}
-
 template <typename HT>
 __global__ void __launch_bounds__(512, 1) k_c3w64(ConvArgs a, int tiles_w, int tiles_hw, int ntiles) {
     constexpr int TH = 8, TW = 32, TP = TH * TW, PCW = TW + 2, PITCH = 40;  // 34 patch columns, 40 slots
@@ -503,10 +444,10 @@ __global__ void __launch_bounds__(512, 1) k_c3w64(ConvArgs a, int tiles_w, int t
         for (int s = 0; s < 18; ++s) pin_loaded(areg[i][s]);
     __syncthreads();
 
-    // XCD-contiguous walk: round i, XCD x = b & 7 takes tiles [i G + x G/8, ... + G/8)
+    // the round walk (rr_tilewalk.h): round i, XCD x = b & 7 takes tiles [i G + x G/8, ... + G/8)
     const int b = (int)blockIdx.x, G = (int)gridDim.x;
-    auto tile_id = [&](int i) { return i * G + (b & 7) * (G >> 3) + (b >> 3); };
-    const pi32x4_t rsX = prsrc(a.x, (unsigned)((long long)a.n * H * W * 64 * 2));
+    auto tile_id = [&](int i) { return xcd_round_tile(b, G, i); };
+    const i32x4_t rsX = make_rsrc(a.x, (unsigned)((long long)a.n * H * W * 64 * 2));
     const unsigned lds0 = (unsigned)(unsigned long long)smem;
     // pieces d = wave + 8 u (50 per patch: waves 0-1 issue 7, the others 6)
     const int nd = (NP - wave + 7) / 8;
@@ -519,10 +460,10 @@ __global__ void __launch_bounds__(512, 1) k_c3w64(ConvArgs a, int tiles_w, int t
             if (d >= NP) break;  // wave-uniform
             const int pr = q / PITCH, pc = q - pr * PITCH;
             const int hh = oh0 - 1 + pr, ww = ow0 - 1 + pc;
-            unsigned off = POOB;
+            unsigned off = OOB;
             if (t < ntiles && pc < PCW && (unsigned)hh < (unsigned)H && (unsigned)ww < (unsigned)W)
                 off = (unsigned)(((((long long)img * H + hh) * W + ww) * 64 + ((lch ^ lrow) << 3)) * 2);
-            pdma16(rsX, off, lds0 + buf * PBYTES + d * 1024);
+            dma16(rsX, off, lds0 + buf * PBYTES + d * 1024);
         }
     };
     // per-lane fragment address bases: pixel fragment j, tap column dx, half-step hs
@@ -540,8 +481,7 @@ __global__ void __launch_bounds__(512, 1) k_c3w64(ConvArgs a, int tiles_w, int t
     bf16_t* __restrict__ Y = (bf16_t*)a.y;
     const bool leaky = a.act == RR_ACT_LEAKY;
     const float slope = a.slope;
-    const int nmine = (ntiles - 1 - (b >> 3) - (b & 7) * (G >> 3)) >= 0
-                          ? (ntiles - 1 - (b & 7) * (G >> 3) - (b >> 3)) / G + 1 : 0;
+    const int nmine = xcd_round_count(b, ntiles, G);
     if (nmine == 0) return;
     // a wave issues the same nd pieces for every patch (past the last tile: zeros),
     // so its counted waits are fixed: nd for the next patch (+ NST stores)
@@ -550,11 +490,11 @@ __global__ void __launch_bounds__(512, 1) k_c3w64(ConvArgs a, int tiles_w, int t
     for (int i = 0; i < nmine; ++i) {
         // patch(i) landed: younger are patch(i + 1) and tile i - 1's stores
         if (nd == 7) {
-            if (i == 0) pwait_barrier<7>();
-            else pwait_barrier<7 + NST>();
+            if (i == 0) vm_wait_barrier<7>();
+            else vm_wait_barrier<7 + NST>();
         } else {
-            if (i == 0) pwait_barrier<6>();
-            else pwait_barrier<6 + NST>();
+            if (i == 0) vm_wait_barrier<6>();
+            else vm_wait_barrier<6 + NST>();
         }
         patch_dma(tile_id(i + 2), (i + 2) % NBUF);
         const char* Ps = smem + (i % NBUF) * PBYTES;
@@ -569,11 +509,11 @@ __global__ void __launch_bounds__(512, 1) k_c3w64(ConvArgs a, int tiles_w, int t
                     asm volatile("" : "+v"(r));  // per-tile opaque copy: bases stay 24 VGPRs
                     base[j][dx][hs] = Ps + r;
                 }
-        pf32x4_t acc[2][FN];
+        f32x4_t acc[2][FN];
 #pragma unroll
         for (int ii = 0; ii < 2; ++ii)
 #pragma unroll
-            for (int j = 0; j < FN; ++j) acc[ii][j] = (pf32x4_t){0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < FN; ++j) acc[ii][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < 18; ++s) {
             const int tap = s >> 1, hs = s & 1, dy = tap / 3, dx = tap % 3;
@@ -615,7 +555,7 @@ __global__ void __launch_bounds__(512, 1) k_c3w64(ConvArgs a, int tiles_w, int t
             *reinterpret_cast<uint4*>(Y + pix * a.ldy + c) = o;
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
 }
 
 template <int TC, int TH, int TW, int WC, int WP, bool ARES, int NSA = 2>
@@ -662,11 +602,10 @@ bool launch_conv3x3(const ConvArgs& a, hipStream_t s, bool f16) {
     if (a.cin == 64 && a.cout == 64 && a.h % 8 == 0 && (mode == 9 || mode == 1)) {
         const int tiles_w = a.w_ / 32, tiles_hw = tiles_w * (a.h / 8);
         const long long ntl = (long long)a.n * tiles_hw;
-        int grid = (int)(ntl < g_c3_cus ? ntl : g_c3_cus) & ~7;
-        if (grid < 8) grid = 8;
+        const int grid = persistent_grid8(ntl, g_c3_cus);
         if (f16) hipLaunchKernelGGL(k_c3w64<f16_t>, dim3(grid), dim3(512), 0, s, a, tiles_w, tiles_hw, (int)ntl);
         else hipLaunchKernelGGL(k_c3w64<bf16_t>, dim3(grid), dim3(512), 0, s, a, tiles_w, tiles_hw, (int)ntl);
-        note_launch("k_c3w64", (unsigned)grid, 512, 0, 1, 1, "64,8,32");  // the XCD-contiguous walk: always on
+        note_launch("k_c3w64", (unsigned)grid, 512, 0, 1, 1, "64,8,32");  // xmap 1: the round walk, always on
         return true;
     }
     if (a.cin == 64 && a.cout == 64 && a.h % 8 == 0) {

@@ -37,76 +37,16 @@
 // Replaces the stride-1 3x3 nn.Conv2d of ResidualBlock (cirtorch/backbones/
 // misc.py:166-172) + the ABN eval BN + leaky_relu (cirtorch/utils/misc.py:175-235).
 #include "rr_internal.h"
+#include "rr_ldsdma.h"
+#include "rr_tilewalk.h"
 
 namespace rr {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float sf32x4_t;
-typedef __attribute__((ext_vector_type(4))) int si32x4_t;
-
-constexpr unsigned SOOB = 0x80000000u;  // voffset beyond every buffer: the DMA writes zeros
-
-// One 16-B-per-lane LDS-DMA wave-instruction: LDS[lds_addr + lane*16] = buf[voff].
-__device__ __forceinline__ void sdma16(si32x4_t rsrc, unsigned voff, unsigned lds_addr) {
-    unsigned keep;
-    lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 0\n\t"  // M0 write -> LDS-DMA: 1 wait state (descriptor: fenced in the rsrc maker)
-        "buffer_load_dwordx4 %1, %2, 0 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(rsrc), "s"(lds_addr)
-        : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void svm_wait() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
-__device__ __forceinline__ si32x4_t srsrc(const void* base, unsigned bytes) {
-    const unsigned long long b = (unsigned long long)base;
-    si32x4_t r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)b);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(b >> 32) & 0xFFFFu));
-    r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-    r.w = 0x00020000;
-    // VALU (readfirstlane) SGPR write -> LDS-DMA descriptor read: 5 wait states, tied to the
-    // registers so no use of the descriptor is scheduled above it (tools/dma_audit.py checks)
-    int x = r.x, y = r.y, z = r.z;
-    asm volatile("s_nop 4" : "+s"(x), "+s"(y), "+s"(z));
-    r.x = x;
-    r.y = y;
-    r.z = z;
-    return r;
-}
-
-__device__ __forceinline__ void sbar() { asm volatile("s_barrier" ::: "memory"); }
-
 struct TileS {
     int img, oh0, ow0;
 };
-
-// XCD-contiguous persistent tile range of this block (blocks are dealt
-// round-robin over the 8 XCDs): XCD x owns [s_x, s_x + n_x), its nb_x blocks
-// stride through it, so the tiles in flight on one XCD are raster neighbours
-// whose halo rows are L2 hits.
-struct TileRange {
-    int s_x, n_x, nb_x, li;
-};
-__device__ __forceinline__ TileRange tile_range(int ntiles) {
-    const int nwg = (int)gridDim.x, bx = (int)blockIdx.x, xcd = bx & 7;
-    const int nt8 = ntiles >> 3, rt8 = ntiles & 7;
-    TileRange r;
-    r.s_x = xcd < rt8 ? xcd * (nt8 + 1) : rt8 * (nt8 + 1) + (xcd - rt8) * nt8;
-    r.n_x = nt8 + (xcd < rt8 ? 1 : 0);
-    r.nb_x = (nwg >> 3) + (xcd < (nwg & 7) ? 1 : 0);
-    r.li = bx >> 3;
-    return r;
-}
 
 // BN scale / shift of this lane's 2 x 8 output channels c0 + 32 * i2 + 8 * kq + r,
 // loaded once, waited for here and made opaque, so that no compiler-inserted
@@ -131,7 +71,7 @@ __device__ __forceinline__ void load_affine_regs(const ConvArgs& a, int c0, int 
 
 // one 16-B epilogue store: fragment pair (acc[2 i2], acc[2 i2 + 1]) of pixel fragment j
 template <typename HT>
-__device__ __forceinline__ void store8(HT* __restrict__ Y, long long o, const sf32x4_t& a0, const sf32x4_t& a1,
+__device__ __forceinline__ void store8(HT* __restrict__ Y, long long o, const f32x4_t& a0, const f32x4_t& a1,
                                        const float (&sc)[8], const float (&sh)[8], float sl) {
     float v[8];
 #pragma unroll
@@ -162,13 +102,13 @@ __global__ void __launch_bounds__(512, 1) k_c3s_w128(ConvArgs a, int tiles_w, in
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2, wn = wave & 3;
-    TileRange tr = tile_range(ntiles);
+    TileRange tr = xcd_tile_range((int)blockIdx.x, ntiles, (int)gridDim.x);
     if (tr.li >= tr.n_x) return;
     const int H = a.h, W = a.w_, Cin = a.cin, nck = Cin >> 6, KS = 9 * nck;
     const unsigned lds0 = (unsigned)(unsigned long long)smem;
     const int lrow = lane >> 3, lch = lane & 7, r16 = lane & 15, kq = lane >> 4;
-    const si32x4_t rsX = srsrc(a.x, (unsigned)((long long)a.n * H * W * Cin * 2));
-    const si32x4_t rsW = srsrc(a.w, (unsigned)(128ll * a.kp * 2));
+    const i32x4_t rsX = make_rsrc(a.x, (unsigned)((long long)a.n * H * W * Cin * 2));
+    const i32x4_t rsW = make_rsrc(a.w, (unsigned)(128ll * a.kp * 2));
 
     float esc[2][8], esh[2][8];
     load_affine_regs(a, grp * 64, kq, esc, esh);
@@ -189,10 +129,10 @@ __global__ void __launch_bounds__(512, 1) k_c3s_w128(ConvArgs a, int tiles_w, in
         const int q = d * 8 + lrow;
         const int pr = q / PC, pcol = q - pr * PC;
         const int hh = tc.oh0 - 1 + pr, ww = tc.ow0 - 1 + pcol;
-        unsigned off = SOOB;
+        unsigned off = OOB;
         if (live && q < NPIX && (unsigned)hh < (unsigned)H && (unsigned)ww < (unsigned)W)
             off = (unsigned)(((((long long)tc.img * H + hh) * W + ww) * Cin + cc * 64 + ((lch ^ lrow) << 3)) * 2);
-        sdma16(rsX, off, lds0 + WBYTES + buf * PB + d * 1024);
+        dma16(rsX, off, lds0 + WBYTES + buf * PB + d * 1024);
     };
     // weight K-step ks (chunk ks / 9, tap ks % 9) into ring stage ks % 3: 128 rows x 128 B
     auto wstep = [&](int ks) {
@@ -201,7 +141,7 @@ __global__ void __launch_bounds__(512, 1) k_c3s_w128(ConvArgs a, int tiles_w, in
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int row = (wave + 8 * i) * 8 + lrow;
-            sdma16(rsW, (unsigned)(row * a.kp * 2) + k0b + (unsigned)((lch ^ lrow) << 4),
+            dma16(rsW, (unsigned)(row * a.kp * 2) + k0b + (unsigned)((lch ^ lrow) << 4),
                    lds0 + (ks % 3) * WST + (wave + 8 * i) * 1024);
         }
     };
@@ -212,13 +152,13 @@ __global__ void __launch_bounds__(512, 1) k_c3s_w128(ConvArgs a, int tiles_w, in
 #pragma unroll
         for (int j = 0; j < 2; ++j) bq[h][j] = (h * 4 + wn) * PC + j * 16 + r16;
 
-    sf32x4_t acc[2][4][2];
+    f32x4_t acc[2][4][2];
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) acc[h][i][j] = (sf32x4_t){0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < 2; ++j) acc[h][i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
     uint4 fa[4][2], fb[2][2];
     const int arow0 = grp * 64 + r16;
 
@@ -243,9 +183,9 @@ __global__ void __launch_bounds__(512, 1) k_c3s_w128(ConvArgs a, int tiles_w, in
     wstep(1 % KS);
 #pragma unroll
     for (int i = 0; i < 6; ++i) piece(cur, 0, 0, i, true);
-    svm_wait<0>();
-    sbar();
-    if (grp == 1) sbar();  // stagger: group 1 runs one barrier behind group 0
+    vm_wait<0>();
+    raw_barrier();
+    if (grp == 1) raw_barrier();  // stagger: group 1 runs one barrier behind group 0
 
     for (;;) {
         const int li_next = tr.li + tr.nb_x;
@@ -282,9 +222,9 @@ __global__ void __launch_bounds__(512, 1) k_c3s_w128(ConvArgs a, int tiles_w, in
                     int k2 = ks + 2;
                     if (k2 >= KS) k2 -= KS;
                     wstep(k2);
-                    sbar();
+                    raw_barrier();
                     mfma_h(0);
-                    sbar();
+                    raw_barrier();
                 }
                 // phase B: pixel half 1; piece `tap` of the next chunk into the other buffer
                 {
@@ -304,18 +244,18 @@ __global__ void __launch_bounds__(512, 1) k_c3s_w128(ConvArgs a, int tiles_w, in
                     // weight K-step ks + 1 (issued in phase A of ks - 1) has landed: only the
                     // younger ops may stay in flight (the previous tile's 8 epilogue stores too at ks = 0)
                     if (tap == 0) {
-                        if (cc == 0) svm_wait<11>();
-                        else svm_wait<3>();
+                        if (cc == 0) vm_wait<11>();
+                        else vm_wait<3>();
                     } else if (tap <= 5) {
-                        svm_wait<4>();
+                        vm_wait<4>();
                     } else if (tap == 6) {
-                        svm_wait<3>();
+                        vm_wait<3>();
                     } else {
-                        svm_wait<2>();
+                        vm_wait<2>();
                     }
-                    sbar();
+                    raw_barrier();
                     mfma_h(1);
-                    sbar();
+                    raw_barrier();
                 }
             }
             pb ^= 1;
@@ -336,13 +276,13 @@ __global__ void __launch_bounds__(512, 1) k_c3s_w128(ConvArgs a, int tiles_w, in
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) acc[h][i][j] = (sf32x4_t){0.f, 0.f, 0.f, 0.f};
+                for (int j = 0; j < 2; ++j) acc[h][i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
         if (!more) break;
         tr.li = li_next;
         cur = nxt;
     }
-    if (grp == 0) sbar();  // equal barrier counts for both groups
-    svm_wait<0>();
+    if (grp == 0) raw_barrier();  // equal barrier counts for both groups
+    vm_wait<0>();
 }
 
 // ---------------------------------------------------------------------------
@@ -361,12 +301,12 @@ __global__ void __launch_bounds__(512, 1) k_c3s_w64(ConvArgs a, int tiles_w, int
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2;
-    TileRange tr = tile_range(ntiles);
+    TileRange tr = xcd_tile_range((int)blockIdx.x, ntiles, (int)gridDim.x);
     if (tr.li >= tr.n_x) return;
     const int H = a.h, W = a.w_;
     const unsigned lds0 = (unsigned)(unsigned long long)smem;
     const int r16 = lane & 15, kq = lane >> 4;
-    const si32x4_t rsX = srsrc(a.x, (unsigned)((long long)a.n * H * W * 64 * 2));
+    const i32x4_t rsX = make_rsrc(a.x, (unsigned)((long long)a.n * H * W * 64 * 2));
 
     float esc[2][8], esh[2][8];
     load_affine_regs(a, 0, kq, esc, esh);
@@ -388,10 +328,10 @@ __global__ void __launch_bounds__(512, 1) k_c3s_w64(ConvArgs a, int tiles_w, int
         const int lc = (lane - ((q >> 1) & 2)) & 3;  // logical chunk whose physical slot this lane fills
         const int pr = q / PC, pcol = q - pr * PC;
         const int hh = tc.oh0 - 1 + pr, ww = tc.ow0 - 1 + pcol;
-        unsigned off = SOOB;
+        unsigned off = OOB;
         if (live && q < NPIX && (unsigned)hh < (unsigned)H && (unsigned)ww < (unsigned)W)
             off = (unsigned)(((((long long)tc.img * H + hh) * W + ww) * 64 + cc * 32 + lc * 8) * 2);
-        sdma16(rsX, off, lds0 + WBYTES + cc * PB + d * 1024);
+        dma16(rsX, off, lds0 + WBYTES + cc * PB + d * 1024);
     };
 
     int bq[2][2];  // patch pixel of (pixel half h, fragment j) at tap (0, 0)
@@ -400,13 +340,13 @@ __global__ void __launch_bounds__(512, 1) k_c3s_w64(ConvArgs a, int tiles_w, int
 #pragma unroll
         for (int j = 0; j < 2; ++j) bq[h][j] = (h * 8 + wave) * PC + j * 16 + r16;
 
-    sf32x4_t acc[2][4][2];
+    f32x4_t acc[2][4][2];
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) acc[h][i][j] = (sf32x4_t){0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < 2; ++j) acc[h][i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
     uint4 fa[4][2], fb[2][2];
 
     auto mfma_h = [&](int h) {
@@ -446,22 +386,22 @@ __global__ void __launch_bounds__(512, 1) k_c3s_w64(ConvArgs a, int tiles_w, int
 
     // ---- prologue: all 18 weight K-steps (9 instructions per wave) + chunk 0 of the first tile
     {
-        const si32x4_t rsW = srsrc(a.w, (unsigned)(64ll * a.kp * 2));
+        const i32x4_t rsW = make_rsrc(a.w, (unsigned)(64ll * a.kp * 2));
 #pragma unroll
         for (int i = 0; i < 9; ++i) {
             const int u = wave + 8 * i;  // instruction u: K-step u / 4, rows (u % 4) * 16 .. + 15
             const int ks = u >> 2, cc = ks / 9, tap = ks - cc * 9;
             const int row = (u & 3) * 16 + (lane >> 2);
             const int lc = (lane - ((row >> 1) & 2)) & 3;
-            sdma16(rsW, (unsigned)((row * a.kp + tap * 64 + cc * 32 + lc * 8) * 2), lds0 + ks * KST + (u & 3) * 1024);
+            dma16(rsW, (unsigned)((row * a.kp + tap * 64 + cc * 32 + lc * 8) * 2), lds0 + ks * KST + (u & 3) * 1024);
         }
     }
     TileS cur = tile_of(tr.s_x + tr.li);
 #pragma unroll
     for (int i = 0; i < 5; ++i) piece(cur, 0, i, true);
-    svm_wait<0>();
-    sbar();
-    if (grp == 1) sbar();  // stagger: group 1 runs one barrier behind group 0
+    vm_wait<0>();
+    raw_barrier();
+    if (grp == 1) raw_barrier();  // stagger: group 1 runs one barrier behind group 0
 
     for (;;) {
         const int li_next = tr.li + tr.nb_x;
@@ -478,9 +418,9 @@ __global__ void __launch_bounds__(512, 1) k_c3s_w64(ConvArgs a, int tiles_w, int
             // chunk 0 of the next tile (buffer 0) in phases 11-13
             if (m == 1) { piece(cur, 1, 2, true); piece(cur, 1, 3, true); }
             if (m == 6) { piece(nxt, 0, 2, more); piece(nxt, 0, 3, more); }
-            sbar();
+            raw_barrier();
             mfma_h(0);
-            sbar();
+            raw_barrier();
             // phase B: pixel half 1
             read_b(2 * m, 1, 0);
             read_b(2 * m + 1, 1, 1);
@@ -489,10 +429,10 @@ __global__ void __launch_bounds__(512, 1) k_c3s_w64(ConvArgs a, int tiles_w, int
             if (m == 5) { piece(nxt, 0, 0, more); piece(nxt, 0, 1, more); }
             if (m == 6) piece(nxt, 0, 4, more);
             // chunk 1 is read from K-step 9 (m = 4), the next tile's chunk 0 from m = 0
-            if (m == 3 || m == 8) svm_wait<0>();
-            sbar();
+            if (m == 3 || m == 8) vm_wait<0>();
+            raw_barrier();
             mfma_h(1);
-            sbar();
+            raw_barrier();
         }
         // ---- epilogue: 8 stores per lane
 #pragma unroll
@@ -510,13 +450,13 @@ __global__ void __launch_bounds__(512, 1) k_c3s_w64(ConvArgs a, int tiles_w, int
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) acc[h][i][j] = (sf32x4_t){0.f, 0.f, 0.f, 0.f};
+                for (int j = 0; j < 2; ++j) acc[h][i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
         if (!more) break;
         tr.li = li_next;
         cur = nxt;
     }
-    if (grp == 0) sbar();  // equal barrier counts for both groups
-    svm_wait<0>();
+    if (grp == 0) raw_barrier();  // equal barrier counts for both groups
+    vm_wait<0>();
 }
 
 }  // namespace

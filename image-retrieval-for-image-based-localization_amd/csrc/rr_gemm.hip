@@ -17,6 +17,8 @@
 //     step's MFMAs, waited with a counted s_waitcnt vmcnt(N) + raw s_barrier
 //     (never __syncthreads(), whose fence would drain the prefetch).
 #include "rr_internal.h"
+#include "rr_ldsdma.h"
+#include "rr_tilewalk.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -25,92 +27,8 @@ namespace rr {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-
-template <typename T> struct Vec2;
-template <> struct Vec2<bf16_t> { static constexpr int N = 8; };
-template <> struct Vec2<f16_t> { static constexpr int N = 8; };
-template <> struct Vec2<float> { static constexpr int N = 4; };
-
-constexpr unsigned OOB = 0x80000000u;  // voffset beyond every buffer: reads as 0
-
-// One 16-B-per-lane LDS-DMA wave-instruction: LDS[m0 + lane*16] = buf[voff].
-// Issued from inline asm so hipcc neither counts it nor inserts a blanket
-// vmcnt(0) before later ds_reads (which it does for compiler-visible LDS-DMA):
-// completion is tracked by the explicit vmcnt(N) below.  M0 is saved/restored.
-typedef __attribute__((ext_vector_type(4))) int i32x4_t;
-__device__ __forceinline__ void dma16(i32x4_t rsrc, unsigned voff, unsigned lds_addr) {
-    unsigned keep;
-    lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);  // wave-uniform by construction; make it provable
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 0\n\t"  // M0 write -> LDS-DMA: 1 wait state (descriptor: fenced in the rsrc maker)
-        "buffer_load_dwordx4 %1, %2, 0 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(rsrc), "s"(lds_addr)
-        : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"i"(N) : "memory");
-}
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ i32x4_t make_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long b = (unsigned long long)base;
-    i32x4_t r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)b);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(b >> 32) & 0xFFFFu));
-    r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-    r.w = 0x00020000;
-    // VALU (readfirstlane) SGPR write -> LDS-DMA descriptor read: 5 wait states, tied to the
-    // registers so no use of the descriptor is scheduled above it (tools/dma_audit.py checks)
-    int x = r.x, y = r.y, z = r.z;
-    asm volatile("s_nop 4" : "+s"(x), "+s"(y), "+s"(z));
-    r.x = x;
-    r.y = y;
-    r.z = z;
-    return r;
-}
 
 __device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
-
-template <typename TO> struct St4;
-template <> struct St4<float> {
-    static __device__ __forceinline__ void st(float* p, const float* v) {
-        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-    static __device__ __forceinline__ void ld(const float* p, float* v) {
-        float4 t = *reinterpret_cast<const float4*>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    }
-};
-template <> struct St4<bf16_t> {
-    static __device__ __forceinline__ void st(bf16_t* p, const float* v) {
-        ushort4 o;
-        o.x = f2bf(v[0]); o.y = f2bf(v[1]); o.z = f2bf(v[2]); o.w = f2bf(v[3]);
-        *reinterpret_cast<ushort4*>(p) = o;
-    }
-    static __device__ __forceinline__ void ld(const bf16_t* p, float* v) {
-        ushort4 t = *reinterpret_cast<const ushort4*>(p);
-        v[0] = bf2f(t.x); v[1] = bf2f(t.y); v[2] = bf2f(t.z); v[3] = bf2f(t.w);
-    }
-};
-
-template <> struct St4<f16_t> {
-    static __device__ __forceinline__ void st(f16_t* p, const float* v) {
-        typedef __attribute__((ext_vector_type(4))) _Float16 h4;
-        *reinterpret_cast<h4*>(p) = (h4){(f16_t)v[0], (f16_t)v[1], (f16_t)v[2], (f16_t)v[3]};
-    }
-    static __device__ __forceinline__ void ld(const f16_t* p, float* v) {
-        typedef __attribute__((ext_vector_type(4))) _Float16 h4;
-        const h4 t = *reinterpret_cast<const h4*>(p);
-        v[0] = (float)t.x; v[1] = (float)t.y; v[2] = (float)t.z; v[3] = (float)t.w;
-    }
-};
 
 // Persistent tile loop: block b walks tiles t = b, b + grid, ... as one
 // flattened stream of (tile, K-step) steps, so the LDS-DMA of the next tile's
@@ -128,7 +46,7 @@ template <> struct St4<f16_t> {
 template <typename T, typename TO, int TC, int TP, int WC, int WP, int KM, bool PERM, int NS, int AK>
 __global__ void __launch_bounds__(64 * WC * WP, ((NS == 2 && AK * TC <= 256) || WC * WP == 8 ? 2 : 1)) k_igemm(ConvArgs a, int tiles_p, int ntiles, int xmap) {
     constexpr bool K1 = KM == 1, tapu = KM == 2;
-    constexpr int VEC = Vec2<T>::N;
+    constexpr int VEC = Vec<T>::N;
     constexpr int BK = 8 * VEC;               // elements per K-step (128 B per row)
     constexpr int ESZ = sizeof(T);
     constexpr int NW = WC * WP;                  // waves per block (4 or 8)
@@ -461,10 +379,10 @@ __global__ void __launch_bounds__(64 * WC * WP, ((NS == 2 && AK * TC <= 256) || 
         // wait until this wave's step-s DMA is done (younger steps may stay in
         // flight; older epilogue VMEM ops are drained too), then barrier: everyone's.
         const int ahead = issued - s - 1;
-        if (NS >= 4 && ahead >= 3) wait_vm_barrier<(NS >= 4 ? 3 : 0) * NLD>();
-        else if (NS >= 3 && ahead == 2) wait_vm_barrier<(NS >= 3 ? 2 : 0) * NLD>();
-        else if (ahead == 1) wait_vm_barrier<AK ? NIB : NLD>();  // AK: a step issues B only (A's one-time load is older)
-        else wait_vm_barrier<0>();
+        if (NS >= 4 && ahead >= 3) vm_wait_barrier<(NS >= 4 ? 3 : 0) * NLD>();
+        else if (NS >= 3 && ahead == 2) vm_wait_barrier<(NS >= 3 ? 2 : 0) * NLD>();
+        else if (ahead == 1) vm_wait_barrier<AK ? NIB : NLD>();  // AK: a step issues B only (A's one-time load is older)
+        else vm_wait_barrier<0>();
         // NS >= 3: ONE barrier per K-step.  The refill is issued after it, into
         // stage (s + NS - 1) % NS == (s - 1) % NS, which every wave finished
         // reading in step s - 1 (all of them have passed this barrier), so the
@@ -649,19 +567,11 @@ __global__ void __launch_bounds__(512, 1) k_gemm8(ConvArgs a, int tiles_p, int n
         __syncthreads();  // visible to every wave before any epilogue reads it
     }
     const int wn = wave & 3;                // 32-column quarter of each quadrant
-    // XCD-contiguous bijective tile order (blocks are dispatched round-robin over 8 XCDs)
-    // Persistent blocks over an XCD-contiguous tile order: XCD x (blocks are
-    // dispatched round-robin over the 8 XCDs) owns the contiguous tile range
-    // [s_x, s_x + n_x) and its nb_x blocks stride through it, so the tiles in
-    // flight on one XCD share A / B rows in its L2.  With one block per tile
-    // (grid = ntiles) this is the plain bijective remap.
-    const int nwg = (int)gridDim.x, bx = (int)blockIdx.x, xcd = bx & 7;
-    const int nt8 = ntiles >> 3, rt8 = ntiles & 7;
-    const int s_x = xcd < rt8 ? xcd * (nt8 + 1) : rt8 * (nt8 + 1) + (xcd - rt8) * nt8;
-    const int n_x = nt8 + (xcd < rt8 ? 1 : 0);
-    const int nb_x = (nwg >> 3) + (xcd < (nwg & 7) ? 1 : 0);
-    int li = bx >> 3;  // this block's local tile index on its XCD
-    if (li >= n_x) return;
+    // Persistent blocks on the range walk (rr_tilewalk.h): the tiles in flight on one XCD
+    // share A / B rows in its L2.  With one block per tile (grid = ntiles) this is the plain
+    // bijective remap.
+    TileRange tr = xcd_tile_range((int)blockIdx.x, ntiles, (int)gridDim.x);
+    if (tr.li >= tr.n_x) return;
     const int H = a.h, W = a.w_, Cin = a.cin;
     const unsigned tap_magic = tapu_magic(a.kh * a.kw);  // tapu_k0
     const int nk = a.kp / KSE;
@@ -705,7 +615,7 @@ __global__ void __launch_bounds__(512, 1) k_gemm8(ConvArgs a, int tiles_p, int n
                 }
             }
     };
-    setup(s_x + li);
+    setup(tr.s_x + tr.li);
     // K-step descriptor, computed once per K-step (not per half-tile issue): the
     // DMA-issue slots sit between the barriers of the staggered schedule, so
     // every instruction there delays the partner group's matrix pipe.  The tap
@@ -799,19 +709,12 @@ __global__ void __launch_bounds__(512, 1) k_gemm8(ConvArgs a, int tiles_p, int n
                         acc[qa][qb][i][j] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_mfma_i32_16x16x64_i8(
                             __builtin_bit_cast(i32x4_t, fa[i][hs]), __builtin_bit_cast(i32x4_t, fb[j][hs]),
                             __builtin_bit_cast(i32x4_t, acc[qa][qb][i][j]), 0, 0, 0));
-                    else if constexpr (std::is_same<T, f16_t>::value)
-                        acc[qa][qb][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                            __builtin_bit_cast(f16x8_t, fa[i][hs]), __builtin_bit_cast(f16x8_t, fb[j][hs]),
-                            acc[qa][qb][i][j], 0, 0, 0);
                     else
-                        acc[qa][qb][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                            __builtin_bit_cast(bf16x8_t, fa[i][hs]), __builtin_bit_cast(bf16x8_t, fb[j][hs]),
-                            acc[qa][qb][i][j], 0, 0, 0);
+                        acc[qa][qb][i][j] = H16<T>::mfma(fa[i][hs], fb[j][hs], acc[qa][qb][i][j]);
                 }
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
     };
-    auto bar = []() { asm volatile("s_barrier" ::: "memory"); };
 
     // ---- prologue: K-step 0 into E (A0 B1 A1 B0), K-step 1's A0 / B1 into O
     auto prologue = [&]() {
@@ -834,10 +737,10 @@ __global__ void __launch_bounds__(512, 1) k_gemm8(ConvArgs a, int tiles_p, int n
         // the previous tile's epilogue stores (issued after this tile's prologue)
         // may still be in flight; an epilogue with a data-dependent store count
         // is waited for entirely
-        if (prev_full) asm volatile("s_waitcnt vmcnt(20)" ::: "memory");  // 4 + ST_FULL
-        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        bar();
-        if (grp == 1) bar();  // stagger: group 1 runs one barrier behind group 0
+        if (prev_full) vm_wait<20>();  // 4 + ST_FULL
+        else vm_wait<4>();
+        raw_barrier();
+        if (grp == 1) raw_barrier();  // stagger: group 1 runs one barrier behind group 0
 
     KD dto = kd1;  // descriptor of K-step `to`, carried from the previous iteration's to + 2
     for (int it = 0; it < nit; ++it) {
@@ -845,40 +748,40 @@ __global__ void __launch_bounds__(512, 1) k_gemm8(ConvArgs a, int tiles_p, int n
         const KD de2 = kdesc(te + 2), do2 = kdesc(to + 2);
         // phases 1-4: K-step te from E; loads: A1-O(to), B0-O(to), A0-E(te+2), B1-E(te+2)
         read_a(0, 0); read_b(0, 0); issue(1, dto, 1);
-        bar(); mfma_q(0, 0); bar();
+        raw_barrier(); mfma_q(0, 0); raw_barrier();
         read_b(0, 1); issue(2, dto, 1);
-        bar(); mfma_q(0, 1); bar();
+        raw_barrier(); mfma_q(0, 1); raw_barrier();
         read_a(0, 1); issue(0, de2, 0);
-        bar(); mfma_q(1, 1); bar();
+        raw_barrier(); mfma_q(1, 1); raw_barrier();
         read_b(0, 0); issue(3, de2, 0);
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // K-step `to` (buffer O) has landed
-        bar(); mfma_q(1, 0); bar();
+        vm_wait<4>();  // K-step `to` (buffer O) has landed
+        raw_barrier(); mfma_q(1, 0); raw_barrier();
         // phases 5-8: K-step to from O; loads: A1-E(te+2), B0-E(te+2), A0-O(to+2), B1-O(to+2)
         read_a(1, 0); read_b(1, 0); issue(1, de2, 0);
-        bar(); mfma_q(0, 0); bar();
+        raw_barrier(); mfma_q(0, 0); raw_barrier();
         read_b(1, 1); issue(2, de2, 0);
-        bar(); mfma_q(0, 1); bar();
+        raw_barrier(); mfma_q(0, 1); raw_barrier();
         read_a(1, 1); issue(0, do2, 1);
-        bar(); mfma_q(1, 1); bar();
+        raw_barrier(); mfma_q(1, 1); raw_barrier();
         read_b(1, 0); issue(3, do2, 1);
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // K-step te + 2 (buffer E) has landed
-        bar(); mfma_q(1, 0); bar();
+        vm_wait<4>();  // K-step te + 2 (buffer E) has landed
+        raw_barrier(); mfma_q(1, 0); raw_barrier();
         dto = do2;
     }
-    if (grp == 0) bar();  // equal barrier counts for both groups: every wave's LDS reads are done
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the trailing (zero) K-step DMAs have landed
+    if (grp == 0) raw_barrier();  // equal barrier counts for both groups: every wave's LDS reads are done
+    vm_wait<0>();  // the trailing (zero) K-step DMAs have landed
 
     // the next tile's prologue DMA flies while this tile's epilogue runs
     const int ec0 = c0, ep0 = p0;
-    li += nb_x;
-    const bool more = li < n_x;
+    tr.li += tr.nb_x;
+    const bool more = tr.li < tr.n_x;
     TO* __restrict__ Y = (TO*)a.y;
     const TO* __restrict__ R = (const TO*)a.res;
     const bool affine = a.flags & RR_CONV_AFFINE;
     const bool resid = a.flags & RR_CONV_RESIDUAL;
     const bool leaky = a.act == RR_ACT_LEAKY;
     if (more) {
-        setup(s_x + li);
+        setup(tr.s_x + tr.li);
         prologue();
     }
     // ---- epilogue: folded BN scale / shift, residual, activation, NHWC store
@@ -1057,10 +960,9 @@ __global__ void __launch_bounds__(512, 1) k_gemm8h(ConvArgs a, int ntiles) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2, wn = wave & 3;
-    // XCD-contiguous bijective tile order (one block per tile)
-    const int bx = (int)blockIdx.x, xcd = bx & 7;
-    const int nt8 = ntiles >> 3, rt8 = ntiles & 7;
-    const int t = (xcd < rt8 ? xcd * (nt8 + 1) : rt8 * (nt8 + 1) + (xcd - rt8) * nt8) + (bx >> 3);
+    // the range walk (rr_tilewalk.h) with one block per tile: an XCD-contiguous bijective order
+    const TileRange tr = xcd_tile_range((int)blockIdx.x, ntiles, (int)gridDim.x);
+    const int t = tr.s_x + tr.li;
     if (t >= ntiles) return;
     const int nk = a.kp / 64;
     const unsigned lds0 = (unsigned)(unsigned long long)smem;
@@ -1139,28 +1041,27 @@ __global__ void __launch_bounds__(512, 1) k_gemm8h(ConvArgs a, int ntiles) {
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
     };
-    auto bar = []() { asm volatile("s_barrier" ::: "memory"); };
 
     // prologue: K-steps 0 and 1 (A0, B0, A1 each); K-step 0's A0 / B0 landed
     issue(0, 0); issue(2, 0); issue(1, 0);
     issue(0, 1); issue(2, 1); issue(1, 1);
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    bar();
-    if (grp == 1) bar();  // stagger: group 1 runs one barrier behind group 0
+    vm_wait<8>();
+    raw_barrier();
+    if (grp == 1) raw_barrier();  // stagger: group 1 runs one barrier behind group 0
     for (int kt = 0; kt < nk; ++kt) {
         // phase A: A0 x B0 of K-step kt; K-step kt + 2's A0 / B0 into the stage kt - 1 used
         read_a(kt, 0); read_b(kt);
         issue(0, kt + 2); issue(2, kt + 2);
-        asm volatile("s_waitcnt vmcnt(10)" ::: "memory");  // K-step kt's A1 has landed
-        bar(); mfma_q(0); bar();
+        vm_wait<10>();  // K-step kt's A1 has landed
+        raw_barrier(); mfma_q(0); raw_barrier();
         // phase B: A1 x B0 (B fragments from registers); K-step kt + 2's A1
         read_a(kt, 1);
         issue(1, kt + 2);
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // K-step kt + 1's A0 / B0 have landed
-        bar(); mfma_q(1); bar();
+        vm_wait<8>();   // K-step kt + 1's A0 / B0 have landed
+        raw_barrier(); mfma_q(1); raw_barrier();
     }
-    if (grp == 0) bar();  // equal barrier counts: every wave's LDS reads are done
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (grp == 0) raw_barrier();  // equal barrier counts: every wave's LDS reads are done
+    vm_wait<0>();
 
     // ---- epilogue: scores (database row c, query p) -> kNN screen or the f32 slab
     float* __restrict__ Y = (float*)a.y;
@@ -1222,14 +1123,9 @@ __global__ void __launch_bounds__(512, 1) k_gemm8s(ConvArgs a, int ntiles) {
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nwg = (int)gridDim.x, bx = (int)blockIdx.x, xcd = bx & 7;
-    const int nt8 = ntiles >> 3, rt8 = ntiles & 7;
-    const int s_x = xcd < rt8 ? xcd * (nt8 + 1) : rt8 * (nt8 + 1) + (xcd - rt8) * nt8;
-    const int n_x = nt8 + (xcd < rt8 ? 1 : 0);
-    const int nb_x = (nwg >> 3) + (xcd < (nwg & 7) ? 1 : 0);
-    const int li = bx >> 3;
-    if (li >= n_x) return;
-    const int my = (n_x - li + nb_x - 1) / nb_x;  // tiles of this block: s_x + li + m * nb_x
+    const TileRange tr = xcd_tile_range((int)blockIdx.x, ntiles, (int)gridDim.x);
+    if (tr.li >= tr.n_x) return;
+    const int my = (tr.n_x - tr.li + tr.nb_x - 1) / tr.nb_x;  // tiles of this block: s_x + li + m * nb_x
     const int nk = a.kp * ESZ / 128;
     const int F = my * nk;                        // (tile, K-step) stream of this block
     const unsigned lds0 = (unsigned)(unsigned long long)smem;
@@ -1257,7 +1153,7 @@ __global__ void __launch_bounds__(512, 1) k_gemm8s(ConvArgs a, int ntiles) {
     int mi = 0, ki = 0;
     const char* arow[2];
     auto set_rows = [&](int m) {
-        const int t = s_x + li + min(m, my - 1) * nb_x;
+        const int t = tr.s_x + tr.li + min(m, my - 1) * tr.nb_x;
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
             const int row = min(t * 256 + 32 * wave + 16 * g + r16, a.cout - 1);
@@ -1301,7 +1197,7 @@ __global__ void __launch_bounds__(512, 1) k_gemm8s(ConvArgs a, int ntiles) {
             if (f0 + u >= F) break;
             // this position's query stage has landed (6 (R - 1) + 4 younger ops) in
             // every wave, and every wave has read the stage the next DMA overwrites
-            asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"i"(6 * (R - 1) + 4) : "memory");
+            vm_wait_barrier<6 * (R - 1) + 4>();
             const char* Bs = smem + cst * HT;
             cst = cst + 1 == NB ? 0 : cst + 1;
 #pragma unroll
@@ -1331,7 +1227,7 @@ __global__ void __launch_bounds__(512, 1) k_gemm8s(ConvArgs a, int ntiles) {
             issue(ar[u]);  // position f + R into the ring slot just consumed
             if (++kc == nk) {
                 // ---- tile epilogue: scores (database row c + r, query p)
-                const int c0 = (s_x + li + m * nb_x) * 256;
+                const int c0 = (tr.s_x + tr.li + m * tr.nb_x) * 256;
                 float* __restrict__ Y = (float*)a.y;
                 if (a.scr_k) {  // stage the survivors, append them in batches (full-wave control flow)
                     ScreenStage st{lds_stage + wave * 3 * ScreenStage::CAP, 0};
@@ -1381,7 +1277,7 @@ __global__ void __launch_bounds__(512, 1) k_gemm8s(ConvArgs a, int ntiles) {
             }
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the trailing positions' operations
+    vm_wait<0>();  // the trailing positions' operations
 }
 
 // ---------------------------------------------------------------------------
@@ -1403,15 +1299,9 @@ __global__ void __launch_bounds__(512, 1) k_gemm8a(ConvArgs a, int tiles_p, int 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2, wn = wave & 3;
-    // persistent blocks over an XCD-contiguous tile range (k_gemm8's walk): XCD x owns
-    // [s_x, s_x + n_x), its nb_x blocks stride through it; grid = ntiles is one tile per block
-    const int nwg = (int)gridDim.x, bx = (int)blockIdx.x, xcd = bx & 7;
-    const int nt8 = ntiles >> 3, rt8 = ntiles & 7;
-    const int s_x = xcd < rt8 ? xcd * (nt8 + 1) : rt8 * (nt8 + 1) + (xcd - rt8) * nt8;
-    const int n_x = nt8 + (xcd < rt8 ? 1 : 0);
-    const int nb_x = (nwg >> 3) + (xcd < (nwg & 7) ? 1 : 0);
-    int li = bx >> 3;
-    if (li >= n_x) return;
+    // persistent blocks on the range walk (rr_tilewalk.h); grid = ntiles is one tile per block
+    TileRange tr = xcd_tile_range((int)blockIdx.x, ntiles, (int)gridDim.x);
+    if (tr.li >= tr.n_x) return;
     const int H = a.h, W = a.w_, Cin = a.cin;
     const unsigned tap_magic = tapu_magic(a.kh * a.kw);  // tapu_k0
     const int nk = a.kp / 64;
@@ -1469,7 +1359,7 @@ __global__ void __launch_bounds__(512, 1) k_gemm8a(ConvArgs a, int tiles_p, int 
                 }
             }
     };
-    setup(s_x + li);
+    setup(tr.s_x + tr.li);
     // K-step descriptor, once per K-step (k_gemm8's KD: no division on the issue path)
     const unsigned kw_magic = tapu_magic(a.kw);
     struct KD {
@@ -1564,7 +1454,6 @@ __global__ void __launch_bounds__(512, 1) k_gemm8a(ConvArgs a, int tiles_p, int 
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
     };
-    auto bar = []() { asm volatile("s_barrier" ::: "memory"); };
     auto prologue = [&]() {
         const KD d0 = kdesc(0), d1 = kdesc(1);
         issue(0, d0); issue(1, d0); issue(2, d0);
@@ -1584,33 +1473,33 @@ __global__ void __launch_bounds__(512, 1) k_gemm8a(ConvArgs a, int tiles_p, int 
         // K-step 0's A0 / B0 have landed: younger are its B1, K-step 1 (8) and the
         // previous tile's epilogue stores; an epilogue with loads / fewer stores is
         // waited for with it
-        if (prev_full) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");  // 8 + ST_FULL
-        else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        if (prev_full) vm_wait<16>();  // 8 + ST_FULL
+        else vm_wait<8>();
         static_assert(8 + ST_FULL == 16, "the counted wait above");
-        bar();
-        if (grp == 1) bar();
+        raw_barrier();
+        if (grp == 1) raw_barrier();
         for (int kt = 0; kt < nk; ++kt) {
             const KD d2 = kdesc(kt + 2);
             // phase A: A0 x B0 of K-step kt; K-step kt + 2's A0 / B0
             read_a(kt); read_b(kt, 0);
             issue(0, d2); issue(1, d2);
-            asm volatile("s_waitcnt vmcnt(10)" ::: "memory");  // K-step kt's B1 has landed
-            bar(); mfma_q(0); bar();
+            vm_wait<10>();  // K-step kt's B1 has landed
+            raw_barrier(); mfma_q(0); raw_barrier();
             // phase B: A0 (registers) x B1; K-step kt + 2's B1
             read_b(kt, 1);
             issue(2, d2);
-            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // K-step kt + 1's A0 / B0 have landed
-            bar(); mfma_q(1); bar();
+            vm_wait<8>();   // K-step kt + 1's A0 / B0 have landed
+            raw_barrier(); mfma_q(1); raw_barrier();
         }
-        if (grp == 0) bar();  // equal barrier counts: every wave's LDS reads of this tile are done
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the trailing (zero) K-step DMAs have landed
+        if (grp == 0) raw_barrier();  // equal barrier counts: every wave's LDS reads of this tile are done
+        vm_wait<0>();  // the trailing (zero) K-step DMAs have landed
 
         // the next tile's prologue DMA flies while this tile's epilogue runs
         const int ep0 = p0;
-        li += nb_x;
-        const bool more = li < n_x;
+        tr.li += tr.nb_x;
+        const bool more = tr.li < tr.n_x;
         if (more) {
-            setup(s_x + li);
+            setup(tr.s_x + tr.li);
             prologue();
         }
         prev_full = !resid && ep0 + 256 <= a.P;
@@ -1658,7 +1547,7 @@ __global__ void __launch_bounds__(512, 1) k_gemm8a(ConvArgs a, int tiles_p, int 
 #pragma unroll
                 for (int j = 0; j < 2; ++j) acc[qb][i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
 }
 
 // 16-bit operands, 1x1 or tap-uniform im2col, an even number of 64-deep

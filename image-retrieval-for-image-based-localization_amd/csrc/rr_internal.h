@@ -121,7 +121,7 @@ template <> struct DT<bf16_t> {
 // 16-bit MFMA operand types of the fused kernels (bf16 or IEEE fp16): one
 // v_mfma_f32_16x16x32_{bf16,f16} on 8 packed values per lane, packing of two
 // floats (round to nearest even) and unpacking of a packed pair.
-typedef __attribute__((ext_vector_type(4))) float h16_f32x4_t;
+typedef __attribute__((ext_vector_type(4))) float h16_f32x4_t;  // the accumulator; rr_ldsdma.h's f32x4_t
 template <typename H> struct H16;
 template <> struct H16<bf16_t> {
     typedef __attribute__((ext_vector_type(8))) __bf16 v8;

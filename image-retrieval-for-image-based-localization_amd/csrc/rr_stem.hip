@@ -17,7 +17,7 @@
 // Map of the file:
 //   shared helpers   tile_origin (tile -> image and pooled origin; every kernel),
 //                    image_src / image_rsrc (an image's base, extent and raw
-//                    buffer, dense or ragged; OOBO, the out-of-image offset; v2
+//                    buffer, dense or ragged; OOB, the out-of-image offset; v2
 //                    and both layouts), load_wfrag (weight fragments with the
 //                    sign flip of pool-before-epilogue; the frame)
 //   v1  k_stem_pool  epilogue on every stem pixel, pooling through LDS order
@@ -44,6 +44,7 @@
 // (the max-pool is exact on the same 16-bit values); v2 and RowPatch are equal
 // bit for bit, S2dPatch sums the same products in another order.
 #include "rr_internal.h"
+#include "rr_ldsdma.h"
 
 #include <type_traits>
 
@@ -51,7 +52,6 @@ namespace rr {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float tf32x4_t;
 
 struct StemArgs {
     const void* x;    // [n][3][h][w] float32, or uint8 pixels (value / 255, torchvision ToTensor)
@@ -112,10 +112,9 @@ __device__ __forceinline__ ImageSrc image_src(const StemArgs& a, const TAB& rt, 
         return {(const char*)a.x + (long long)img * 3 * ((long long)a.h * a.w_) * (U8 ? 1 : 4), a.h, a.w_};
 }
 // The image as one raw buffer (3 planes) with 32-bit byte offsets.  A pixel
-// outside the image gets the offset OOBO, past any buffer (reads 0) -- never a
+// outside the image gets the offset OOB (rr_ldsdma.h), past any buffer (reads 0) -- never a
 // negative one -- and is zeroed after normalisation where it is outside the
 // batch map too.
-constexpr unsigned OOBO = 0x80000000u;
 template <bool U8>
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t image_rsrc(const ImageSrc& s) {
     return __builtin_amdgcn_make_buffer_rsrc((void*)s.base, (short)0, (int)(3 * (s.h * s.w) * (U8 ? 1 : 4)),
@@ -252,9 +251,9 @@ __global__ void __launch_bounds__(NT) k_stem_pool(StemArgs a, TAB rt, int tiles_
             const int nn = n < NP ? n : NP - 1;
             const int sr = nn / SC, sc = nn - sr * SC;
             const char* pb = patch + ((2 * sr) * IC + 2 * sc + 2 * q) * 8;
-            tf32x4_t acc[4];
+            f32x4_t acc[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i] = (tf32x4_t){0.f, 0.f, 0.f, 0.f};
+            for (int i = 0; i < 4; ++i) acc[i] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int m = 0; m < 7; ++m) {
                 const uint4 b = *reinterpret_cast<const uint4*>(pb + m * IC * 8);
@@ -409,8 +408,8 @@ __global__ void __launch_bounds__(NT) k_stem_pool2(StemArgs a, int tiles_w, int 
             const int ih = ir0 + r, iw = ic0 + c;
             const bool rok = (unsigned)ih < (unsigned)H;
             const int o = (ih * W + iw) * ESZ;
-            const unsigned off0 = rok && (unsigned)iw < (unsigned)W ? (unsigned)o : OOBO;
-            const unsigned off1 = rok && (unsigned)(iw + 1) < (unsigned)W ? (unsigned)(o + ESZ) : OOBO;
+            const unsigned off0 = rok && (unsigned)iw < (unsigned)W ? (unsigned)o : OOB;
+            const unsigned off1 = rok && (unsigned)(iw + 1) < (unsigned)W ? (unsigned)(o + ESZ) : OOB;
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) {
                 const unsigned po = (unsigned)(ch * iplane * ESZ);
@@ -653,8 +652,8 @@ struct RowPatchT {
             const bool rok = (unsigned)ih < (unsigned)hi;
             if constexpr (U8) {  // one byte load per pixel (out of the image: raw 0)
                 const int o = (ih * wi + iw) * ESZ;
-                const unsigned off0 = rok && (unsigned)iw < (unsigned)wi ? (unsigned)o : OOBO;
-                const unsigned off1 = rok && (unsigned)(iw + 1) < (unsigned)wi ? (unsigned)(o + ESZ) : OOBO;
+                const unsigned off0 = rok && (unsigned)iw < (unsigned)wi ? (unsigned)o : OOB;
+                const unsigned off1 = rok && (unsigned)(iw + 1) < (unsigned)wi ? (unsigned)(o + ESZ) : OOB;
 #pragma unroll
                 for (int ch = 0; ch < 3; ++ch) {
                     const unsigned po = (unsigned)(ch * iplane * ESZ);
@@ -667,7 +666,7 @@ struct RowPatchT {
                 // pass the buffer end, which the per-dword range check reads as 0
                 // (tools/oob_probe.hip) -- that value is never used
                 const int bw = pair_base(iw, wi);
-                const unsigned offp = rok ? (unsigned)((ih * wi + bw) * ESZ) : OOBO;
+                const unsigned offp = rok ? (unsigned)((ih * wi + bw) * ESZ) : OOB;
 #pragma unroll
                 for (int ch = 0; ch < 3; ++ch) {
                     const unsigned po = (unsigned)(ch * iplane * ESZ);
@@ -830,7 +829,7 @@ struct S2dPatch {
             for (int e = 0; e < 4; ++e) {  // e = a * 2 + b
                 const int y = ih + (e >> 1), x = iw + (e & 1);
                 off[e] = ((unsigned)y < (unsigned)hi && (unsigned)x < (unsigned)wi) ? (unsigned)((y * wi + x) * ESZ)
-                                                                                     : OOBO;
+                                                                                     : OOB;
             }
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) {

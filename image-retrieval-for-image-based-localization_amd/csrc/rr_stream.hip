@@ -22,12 +22,11 @@
 //     bf16 pack, one 16-B store per (fragment pair, pixel).
 // HBM traffic = x once (per channel slice) + residual once + y once.
 #include "rr_internal.h"
+#include "rr_ldsdma.h"
 
 namespace rr {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) float sf32x4_t;
 
 // LDS image of the weight slice: row r (packed output channel), 16-B chunk c
 // lives at r*K*2 + ((c ^ f(r)) * 16); f makes every ds_read_b128 lane group of
@@ -153,11 +152,11 @@ __global__ void __launch_bounds__(64 * NW) k_stream1x1(ConvArgs a, int nslices, 
                 // the (loop-invariant) weight slice into VGPRs, which would spill
                 int abase = 0;
                 asm volatile("" : "+v"(abase));
-                sf32x4_t acc[2][FN];
+                f32x4_t acc[2][FN];
 #pragma unroll
                 for (int h = 0; h < 2; ++h)
 #pragma unroll
-                    for (int j = 0; j < FN; ++j) acc[h][j] = (sf32x4_t){0.f, 0.f, 0.f, 0.f};
+                    for (int j = 0; j < FN; ++j) acc[h][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int kk = 0; kk < NK; ++kk)
 #pragma unroll
@@ -331,7 +330,7 @@ __global__ void __launch_bounds__(512) k_stream_pair(PairArgs a) {
             for (int i2 = 0; i2 < NR3; ++i2) {
                 int abase = 0;
                 asm volatile("" : "+v"(abase));  // keep the weight fragments in LDS (no hoisting into VGPRs)
-                sf32x4_t acc[2] = {(sf32x4_t){0.f, 0.f, 0.f, 0.f}, (sf32x4_t){0.f, 0.f, 0.f, 0.f}};
+                f32x4_t acc[2] = {(f32x4_t){0.f, 0.f, 0.f, 0.f}, (f32x4_t){0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
                 for (int kk = 0; kk < NK3; ++kk)
 #pragma unroll
@@ -347,7 +346,7 @@ __global__ void __launch_bounds__(512) k_stream_pair(PairArgs a) {
                     v[4 + r] = acc[1][r] * sS3[c + 4 + r] + sH3[c + 4 + r];
                 }
                 if constexpr (PROJ) {  // shortcut = proj_bn(proj_conv(x_in)), kept in f32
-                    sf32x4_t pacc[2] = {(sf32x4_t){0.f, 0.f, 0.f, 0.f}, (sf32x4_t){0.f, 0.f, 0.f, 0.f}};
+                    f32x4_t pacc[2] = {(f32x4_t){0.f, 0.f, 0.f, 0.f}, (f32x4_t){0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
                     for (int kk = 0; kk < NK3; ++kk)
 #pragma unroll
@@ -381,9 +380,9 @@ __global__ void __launch_bounds__(512) k_stream_pair(PairArgs a) {
             }
             load(d, strip_of(i + D));  // refill this slot: strip i + D
             // ---- z = act1(W1 y * s1 + h1), y straight from registers
-            sf32x4_t zacc[NF1];
+            f32x4_t zacc[NF1];
 #pragma unroll
-            for (int o = 0; o < NF1; ++o) zacc[o] = (sf32x4_t){0.f, 0.f, 0.f, 0.f};
+            for (int o = 0; o < NF1; ++o) zacc[o] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kk = 0; kk < NK1; ++kk) {
                 int abase = 0;
@@ -439,46 +438,6 @@ __global__ void __launch_bounds__(512) k_stream_pair(PairArgs a) {
 // fragment hits 16 distinct 16-B bank groups.  MFMA accumulation order per
 // element equals the two unfused k_stream1x1 launches (K-steps in order), so
 // y and z are bit-identical to them.
-typedef __attribute__((ext_vector_type(4))) int si32x4_t;
-
-// A value loaded once before a loop (weights kept in VGPRs): passing it through an
-// empty asm makes the asm its producer, so the compiler's wait for the load sits
-// before the loop instead of (counted against the loop's own LDS-DMA / stores,
-// which it cannot see) in front of every use inside it.
-__device__ __forceinline__ void pin_loaded(uint4& v) {
-    asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w));
-}
-
-__device__ __forceinline__ void sdma16(si32x4_t rsrc, unsigned voff, unsigned lds_addr) {
-    unsigned keep;
-    lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 0\n\t"  // M0 write -> LDS-DMA: 1 wait state (descriptor: fenced in the rsrc maker)
-        "buffer_load_dwordx4 %1, %2, 0 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(rsrc), "s"(lds_addr)
-        : "memory");
-}
-__device__ __forceinline__ si32x4_t srsrc(const void* base, unsigned bytes) {
-    const unsigned long long b = (unsigned long long)base;
-    si32x4_t r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)b);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(b >> 32) & 0xFFFFu));
-    r.z = __builtin_amdgcn_readfirstlane((int)bytes);  // reads past the end return zeros
-    r.w = 0x00020000;
-    // VALU (readfirstlane) SGPR write -> LDS-DMA descriptor read: 5 wait states, tied to the
-    // registers so no use of the descriptor is scheduled above it (tools/dma_audit.py checks)
-    int x = r.x, y = r.y, z = r.z;
-    asm volatile("s_nop 4" : "+s"(x), "+s"(y), "+s"(z));
-    r.x = x;
-    r.y = y;
-    r.z = z;
-    return r;
-}
-
 struct PairMidArgs {
     const bf16_t* x;    // [P][128]
     const bf16_t* w3;   // [512][128] PERM32 rows
@@ -533,8 +492,8 @@ __global__ void __launch_bounds__(512, 1) k_pair_mid(PairMidArgs a) {
     const int ntiles = (int)((P + TP - 1) / TP);
     const int t0 = (int)blockIdx.x, G = (int)gridDim.x;
     if (t0 >= ntiles) return;
-    const si32x4_t rsX = srsrc(a.x, (unsigned)(P * K3 * 2));
-    const si32x4_t rsR = srsrc(a.res, (unsigned)(P * C3 * 2));
+    const i32x4_t rsX = make_rsrc(a.x, (unsigned)(P * K3 * 2));
+    const i32x4_t rsR = make_rsrc(a.res, (unsigned)(P * C3 * 2));
     const unsigned lds0 = (unsigned)(unsigned long long)smem;
     const unsigned ldsX = lds0 + 2 * RB;
     // x tile: 16 wave-instructions of 4 pixels x 256 B (2 per wave)
@@ -543,7 +502,7 @@ __global__ void __launch_bounds__(512, 1) k_pair_mid(PairMidArgs a) {
         for (int u = 0; u < 2; ++u) {
             const int d = 2 * wave + u, px = 4 * d + (lane >> 4), slot = lane & 15;
             const unsigned off = (unsigned)(((long long)t * TP + px) * (K3 * 2)) + (unsigned)((slot ^ (px & 15)) << 4);
-            sdma16(rsX, off, ldsX + d * 1024);
+            dma16(rsX, off, ldsX + d * 1024);
         }
     };
     // residual tile: 64 wave-instructions of one pixel x 1 KiB (8 per wave)
@@ -552,7 +511,7 @@ __global__ void __launch_bounds__(512, 1) k_pair_mid(PairMidArgs a) {
         for (int u = 0; u < 8; ++u) {
             const int px = 8 * wave + u;
             const unsigned off = (unsigned)(((long long)t * TP + px) * (C3 * 2)) + (unsigned)((lane ^ (px & 15)) << 4);
-            sdma16(rsR, off, lds0 + buf * RB + px * 1024);
+            dma16(rsR, off, lds0 + buf * RB + px * 1024);
         }
     };
     const bool leaky3 = a.act3 == RR_ACT_LEAKY, leaky1 = a.act1 == RR_ACT_LEAKY;
@@ -563,19 +522,19 @@ __global__ void __launch_bounds__(512, 1) k_pair_mid(PairMidArgs a) {
         const int cur = k & 1;
         const bool more = t + G < ntiles;
         // x(t), r(t) landed; only the previous tile's 4 z stores may stay in flight
-        if (k == 0) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
+        if (k == 0) vm_wait_barrier<0>();
+        else vm_wait_barrier<4>();
         if (more) dma_r(t + G, cur ^ 1);
         const char* X = smem + 2 * RB;
         char* RY = smem + cur * RB;
         // ---- stage 1: y = act3(W3 x * s3 + h3 + r), one 32-channel pair at a time
 #pragma unroll
         for (int i2 = 0; i2 < 2; ++i2) {
-            h16_f32x4_t acc[2][4];
+            f32x4_t acc[2][4];
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[h][j] = (h16_f32x4_t){0.f, 0.f, 0.f, 0.f};
+                for (int j = 0; j < 4; ++j) acc[h][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
                 uint4 bx[4];
@@ -629,12 +588,12 @@ __global__ void __launch_bounds__(512, 1) k_pair_mid(PairMidArgs a) {
             }
         }
         // y tile complete in LDS; x buffer free
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        lds_barrier();
         if (more) dma_x(t + G);
         // ---- stage 2: z = act1(W1 y * s1 + h1), K = 512 from the LDS y tile
-        h16_f32x4_t zacc[4];
+        f32x4_t zacc[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) zacc[j] = (h16_f32x4_t){0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 4; ++j) zacc[j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk) {
             uint4 by[4];
@@ -667,7 +626,7 @@ __global__ void __launch_bounds__(512, 1) k_pair_mid(PairMidArgs a) {
             }
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
 }
 
 // The same boundary with a deeper HBM stream (round 6, the default; RR_TUNE_PAIR_MID = 0 runs
@@ -718,22 +677,22 @@ __global__ void __launch_bounds__(512, 1) k_pair_mid_ring(PairMidArgs a) {
         for (int kk = 0; kk < 4; ++kk) pin_loaded(a3[i][kk]);
 #pragma unroll
     for (int kk = 0; kk < 16; ++kk) pin_loaded(a1[kk]);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the weights: the counted waits below see only DMA / stores
+    vm_wait<0>();  // the weights: the counted waits below see only DMA / stores
     __syncthreads();
 
     const long long P = a.P;
     const int ntiles = (int)((P + TP - 1) / TP);
     const int t0 = (int)blockIdx.x, G = (int)gridDim.x;
     if (t0 >= ntiles) return;
-    const si32x4_t rsX = srsrc(a.x, (unsigned)(P * K3 * 2));
-    const si32x4_t rsR = srsrc(a.res, (unsigned)(P * C3 * 2));
+    const i32x4_t rsX = make_rsrc(a.x, (unsigned)(P * K3 * 2));
+    const i32x4_t rsR = make_rsrc(a.res, (unsigned)(P * C3 * 2));
     const unsigned lds0 = (unsigned)(unsigned long long)smem;
     const unsigned ldsX = lds0 + NR * RB;
     // x tile: 8 wave-instructions of 4 pixels x 256 B (one per wave)
     auto dma_x = [&](int t, int xb) {
         const int px = 4 * wave + (lane >> 4), slot = lane & 15;
         const unsigned off = (unsigned)(((long long)t * TP + px) * (K3 * 2)) + (unsigned)((slot ^ (px & 15)) << 4);
-        sdma16(rsX, off, ldsX + xb * XB + wave * 1024);
+        dma16(rsX, off, ldsX + xb * XB + wave * 1024);
     };
     // residual tile: 32 wave-instructions of one pixel x 1 KiB (4 per wave)
     auto dma_r = [&](int t, int buf) {
@@ -741,7 +700,7 @@ __global__ void __launch_bounds__(512, 1) k_pair_mid_ring(PairMidArgs a) {
         for (int u = 0; u < 4; ++u) {
             const int px = 4 * wave + u;
             const unsigned off = (unsigned)(((long long)t * TP + px) * (C3 * 2)) + (unsigned)((lane ^ (px & 15)) << 4);
-            sdma16(rsR, off, lds0 + buf * RB + px * 1024);
+            dma16(rsR, off, lds0 + buf * RB + px * 1024);
         }
     };
     const bool leaky3 = a.act3 == RR_ACT_LEAKY, leaky1 = a.act1 == RR_ACT_LEAKY;
@@ -752,8 +711,8 @@ __global__ void __launch_bounds__(512, 1) k_pair_mid_ring(PairMidArgs a) {
     dma_r(t0 + 2 * G, 2);
     for (int k = 0, t = t0; t < ntiles; ++k, t += G) {
         const int cur = k & 3, xc = k & 1;
-        if (k == 0) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(10)\n\ts_barrier" ::: "memory");
+        if (k == 0) vm_wait_barrier<8>();
+        else vm_wait_barrier<10>();
         dma_x(t + G, xc ^ 1);
         dma_r(t + 3 * G, (k + 3) & 3);
         const char* X = smem + NR * RB + xc * XB;
@@ -761,11 +720,11 @@ __global__ void __launch_bounds__(512, 1) k_pair_mid_ring(PairMidArgs a) {
         // ---- stage 1: y = act3(W3 x * s3 + h3 + r), one 32-channel pair at a time
 #pragma unroll
         for (int i2 = 0; i2 < 2; ++i2) {
-            h16_f32x4_t acc[2][2];
+            f32x4_t acc[2][2];
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) acc[h][j] = (h16_f32x4_t){0.f, 0.f, 0.f, 0.f};
+                for (int j = 0; j < 2; ++j) acc[h][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
                 uint4 bx[2];
@@ -819,11 +778,11 @@ __global__ void __launch_bounds__(512, 1) k_pair_mid_ring(PairMidArgs a) {
             }
         }
         // y tile complete in LDS; the x buffer of this tile is free
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        lds_barrier();
         // ---- stage 2: z = act1(W1 y * s1 + h1), K = 512 from the LDS y tile
-        h16_f32x4_t zacc[2];
+        f32x4_t zacc[2];
 #pragma unroll
-        for (int j = 0; j < 2; ++j) zacc[j] = (h16_f32x4_t){0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 2; ++j) zacc[j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk) {
             uint4 by[2];
@@ -855,7 +814,7 @@ __global__ void __launch_bounds__(512, 1) k_pair_mid_ring(PairMidArgs a) {
             }
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
 }
 
 
@@ -941,9 +900,9 @@ __global__ void __launch_bounds__(512, 1) k_wres1x1(WresArgs a) {
     const int ntiles = (int)((P + TP - 1) / TP);
     if (bi >= ntiles) return;
     const long long nimg = P / ((long long)a.ho * a.wo);
-    const si32x4_t rsX = srsrc(a.x, (unsigned)(nimg * a.h * a.w_ * XRB));
-    si32x4_t rsR = rsX;
-    if constexpr (RES) rsR = srsrc(a.res + c0, (unsigned)(P * a.ldy * 2 - (long long)c0 * 2));
+    const i32x4_t rsX = make_rsrc(a.x, (unsigned)(nimg * a.h * a.w_ * XRB));
+    i32x4_t rsR = rsX;
+    if constexpr (RES) rsR = make_rsrc(a.res + c0, (unsigned)(P * a.ldy * 2 - (long long)c0 * 2));
     const unsigned lds0 = (unsigned)(unsigned long long)smem;
     const int hw = a.ho * a.wo;
     auto x_row = [&](unsigned p) -> unsigned {  // input row of output pixel p (past the end: past the buffer)
@@ -959,7 +918,7 @@ __global__ void __launch_bounds__(512, 1) k_wres1x1(WresArgs a) {
             constexpr int CPR = XRB / 16;
             const int d = NDX * wave + u, px = d * (1024 / XRB) + lane / CPR, slot = lane % CPR;
             const unsigned off = x_row((unsigned)(t * TP + px)) * XRB + (unsigned)((slot ^ (px & 15)) << 4);
-            sdma16(rsX, off, lds0 + buf * BUF + d * 1024);
+            dma16(rsX, off, lds0 + buf * BUF + d * 1024);
         }
         if constexpr (RES) {
 #pragma unroll
@@ -967,7 +926,7 @@ __global__ void __launch_bounds__(512, 1) k_wres1x1(WresArgs a) {
                 constexpr int CPR = RRB / 16;
                 const int d = NDR * wave + u, px = d * (1024 / RRB) + lane / CPR, slot = lane % CPR;
                 const unsigned off = (unsigned)(((long long)t * TP + px) * a.ldy * 2) + (unsigned)((slot ^ (px & 15)) << 4);
-                sdma16(rsR, off, lds0 + buf * BUF + XB + d * 1024);
+                dma16(rsR, off, lds0 + buf * BUF + XB + d * 1024);
             }
         }
     };
@@ -988,29 +947,29 @@ __global__ void __launch_bounds__(512, 1) k_wres1x1(WresArgs a) {
             // tile t's DMA landed: still in flight after it may be tile t + G's DMA and
             // (k > 0) this wave's stores of tile t - G, issued in that order
             if (t + G < ntiles) {
-                if (k == 0) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(ND) : "memory");
-                else asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(ND + NST) : "memory");
+                if (k == 0) vm_wait_barrier<ND>();
+                else vm_wait_barrier<ND + NST>();
             } else {
-                if (k == 0) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(NST) : "memory");
+                if (k == 0) vm_wait_barrier<0>();
+                else vm_wait_barrier<NST>();
             }
             // every wave is past tile t - G: its buffer takes tile t + 2G
             if (t + 2 * G < ntiles) dma(t + 2 * G, (k + 2) % NBUF);
         } else {
             // tile t's DMA landed: younger are tiles t + G .. t + (DA - 1) G and (k > 0) the
             // stores of tile t - G (older stores are waited for too: an over-wait, safe)
-            if (k == 0) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"((DA - 1) * ND) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"((DA - 1) * ND + NST) : "memory");
+            if (k == 0) vm_wait_barrier<(DA - 1) * ND>();
+            else vm_wait_barrier<(DA - 1) * ND + NST>();
             // every wave is past tile t - G: its buffer takes tile t + DA G
             dma(t + DA * G, (k + DA) % NBUF);
         }
         const char* X = smem + cur * BUF;
         const char* Rt = X + XB;
-        h16_f32x4_t acc[NI][NJ];
+        f32x4_t acc[NI][NJ];
 #pragma unroll
         for (int i = 0; i < NI; ++i)
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) acc[i][j] = (h16_f32x4_t){0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < NJ; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kk = 0; kk < NK; ++kk) {
             uint4 bx[NJ];
@@ -1065,7 +1024,7 @@ __global__ void __launch_bounds__(512, 1) k_wres1x1(WresArgs a) {
             }
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
 }
 
 

@@ -8,13 +8,16 @@
 //    arguments must return RR_EINVAL / RR_ENOSPACE with a message, never touch memory);
 //  * the ragged-batch table packing (> 64 images -> several launches, host arrays
 //    of pointers and extents read in full);
-//  * rr_set_tuning, rr_last_error, rr_comm_unique_id (RCCL dlopen'ed).
+//  * rr_set_tuning, rr_last_error, rr_comm_unique_id (RCCL dlopen'ed);
+//  * the persistent kernels' tile walks (rr_tilewalk.h), exhaustively over small grids.
 // Exit status 0 and the last line "ASAN-DRIVER OK" when nothing was reported.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
+#include "../../image-retrieval-for-image-based-localization_amd/csrc/rr_tilewalk.h"
 #include "../../image-retrieval-for-image-based-localization_amd/csrc/rr_workspace.h"
 #include "../../include/rr.h"
 
@@ -80,9 +83,69 @@ static void arena_case() {
     EXPECT(edge.take<char>(SIZE_MAX - 300) == nullptr && edge.bytes() == SIZE_MAX && !edge.fits());
 }
 
+// every tile of [0, ntiles) exactly once, and the tiles of each XCD (block & 7) one contiguous run
+static bool covers(const std::vector<int>& xcd_of_tile, const std::vector<int>& times) {
+    bool seen[8] = {};
+    for (size_t t = 0; t < times.size(); ++t) {
+        if (times[t] != 1) return false;
+        if (t > 0 && xcd_of_tile[t] == xcd_of_tile[t - 1]) continue;
+        if (seen[xcd_of_tile[t]]) return false;   // a second run of this XCD
+        seen[xcd_of_tile[t]] = true;
+    }
+    return true;
+}
+
+static void tilewalk_case() {
+    for (int ntiles = 0; ntiles <= 80; ++ntiles) {
+        for (int grid = 8; grid <= 40; ++grid) {        // range walk: any grid of at least 8 blocks
+            std::vector<int> xcd(ntiles, -1), times(ntiles, 0);
+            bool inside = true;
+            for (int b = 0; b < grid; ++b) {
+                const rr::TileRange r = rr::xcd_tile_range(b, ntiles, grid);
+                const rr::XcdTiles x = rr::xcd_tiles(b, ntiles);
+                EXPECT(x.s_x == r.s_x && x.n_x == r.n_x);
+                for (int m = 0; r.li + m * r.nb_x < r.n_x; ++m) {
+                    const int t = r.s_x + r.li + m * r.nb_x;
+                    if (t < 0 || t >= ntiles) { inside = false; continue; }
+                    ++times[t];
+                    xcd[t] = b & 7;
+                }
+            }
+            EXPECT(inside && covers(xcd, times));
+        }
+        for (int grid = 8; grid <= 40; grid += 8) {     // round walk: grids that are multiples of 8
+            std::vector<int> xcd(ntiles, -1), times(ntiles, 0);
+            bool inside = true;
+            for (int b = 0; b < grid; ++b) {
+                const int n = rr::xcd_round_count(b, ntiles, grid);
+                for (int i = 0; i < n; ++i) {
+                    const int t = rr::xcd_round_tile(b, grid, i);
+                    if (t < 0 || t >= ntiles) { inside = false; continue; }
+                    ++times[t];
+                    xcd[t] = b & 7;
+                }
+                EXPECT(rr::xcd_round_tile(b, grid, n) >= ntiles);   // the count stops at the first missing tile
+            }
+            // contiguous per XCD inside each round of `grid` tiles
+            bool ok = inside;
+            for (int t0 = 0; t0 < ntiles && ok; t0 += grid) {
+                const int n = std::min(grid, ntiles - t0);
+                ok = covers(std::vector<int>(xcd.begin() + t0, xcd.begin() + t0 + n),
+                            std::vector<int>(times.begin() + t0, times.begin() + t0 + n));
+            }
+            EXPECT(ok);
+        }
+        for (int cus : {8, 100, 256}) {
+            const int g = rr::persistent_grid8(ntiles, cus);
+            EXPECT(g % 8 == 0 && g >= 8 && g <= std::max(8, cus));
+        }
+    }
+}
+
 int main() {
     EXPECT(rr_version() > 0);
     arena_case();
+    tilewalk_case();
     EXPECT(rr_last_error() != nullptr);
 
     // --- workspace sizing

@@ -5,8 +5,9 @@ does not pad for hazards.  Two hazards concern it (cdna_hip_programming.md §5.7
   * M0 written by `s_mov_b32 m0, ...` -> the LDS-DMA that reads it: 1 wait state;
   * an SGPR written by a VALU instruction (v_readfirstlane / v_readlane / a VALU with an SGPR
     destination) -> the LDS-DMA reading it as its buffer descriptor: 5 wait states.
-The issue sequence carries only the first (`s_nop 0`); the descriptors are produced by
-make_rsrc, which ends in a wait-state fence tied to the descriptor registers.  This audit
+The issue sequence (dma16, csrc/rr_ldsdma.h: its one source) carries only the first (`s_nop 0`);
+the descriptors are produced by make_rsrc beside it, which ends in a wait-state fence tied to the
+descriptor registers.  This audit
 disassembles the gfx950 code objects of csrc/build/*.o and walks back from every LDS-DMA in
 program order: it fails if a VALU SGPR write to the descriptor lies within 5 wait states, if
 fewer than 1 wait state separates the M0 write from the DMA, or if any instruction other than
@@ -28,14 +29,22 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILD = os.path.join(REPO, "image-retrieval-for-image-based-localization_amd", "csrc", "build")
 
 
-def disassemble(obj, tmp):
+def code_object(obj, tmp):
+    """the gfx950 code object of a host object file, unbundled into tmp; None: no device code"""
     fb = os.path.join(tmp, "fb.bin")
     co = os.path.join(tmp, "g.co")
     if subprocess.run([LLVM + "/llvm-objcopy", "--dump-section", ".hip_fatbin=" + fb, obj],
                       capture_output=True).returncode:
-        return []  # no device code in this object
+        return None
     subprocess.run([LLVM + "/clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
                     "--input=" + fb, "--output=" + co, "--unbundle"], check=True, capture_output=True)
+    return co
+
+
+def disassemble(obj, tmp):
+    co = code_object(obj, tmp)
+    if co is None:
+        return []
     out = subprocess.run([LLVM + "/llvm-objdump", "-d", co], check=True, capture_output=True, text=True).stdout
     return out.splitlines()
 
