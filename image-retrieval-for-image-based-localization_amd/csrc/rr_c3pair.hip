@@ -27,6 +27,7 @@
 // in LDS, so the launch reads the block input instead of t1.
 #include "rr_internal.h"
 #include "rr_ldsdma.h"
+#include "rr_epilogue.h"
 #include "rr_tilewalk.h"
 
 #ifndef C3P_IG2
@@ -212,10 +213,7 @@ __global__ void __launch_bounds__(512, 1) k_c3pair(C3PairArgs a, int tiles_w, in
                     const int q = (wpx * 2 + (j >> 1)) * PITCH + (j & 1) * 16 + lc + dx;  // tile pixel wpx*64 + j*16
                     base[j][dx][hs] = sPatch + q * 128 + (((kq + 4 * hs) ^ (q & 7)) << 4);
                 }
-#pragma unroll
-        for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-            for (int j = 0; j < FN; ++j) acc[ii][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+        RR_ZERO(2, acc);
 #pragma unroll
         for (int s = 0; s < 18; ++s) {
             const int tap = s >> 1, hs = s & 1, dy = tap / 3, dx = tap % 3;
@@ -249,8 +247,7 @@ __global__ void __launch_bounds__(512, 1) k_c3pair(C3PairArgs a, int tiles_w, in
                 for (int kk = 0; kk < 2; ++kk)
                     bx[kk] = *reinterpret_cast<const uint4*>(slot + (((4 * kk + kq) ^ (q & 7)) << 4));
                 f32x4_t c0[4];
-#pragma unroll
-                for (int ii = 0; ii < 4; ++ii) c0[ii] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+                RR_ZERO(1, c0);
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
@@ -262,21 +259,11 @@ __global__ void __launch_bounds__(512, 1) k_c3pair(C3PairArgs a, int tiles_w, in
                 for (int i2 = 0; i2 < 2; ++i2) {
                     const int c = 32 * i2 + 8 * kq;
                     float v[8];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        v[r] = c0[2 * i2][r] * sS0[c + r] + sH0[c + r];
-                        v[4 + r] = c0[2 * i2 + 1][r] * sS0[c + 4 + r] + sH0[c + 4 + r];
-                    }
-                    if (leaky0) {
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope0;
-                    }
+                    RR_BN_PAIR(c0[2 * i2], c0[2 * i2 + 1], sS0 + c, sH0 + c, v);
+                    if (leaky0) RR_LEAKY(8, v, a.slope0);
                     uint4 o = make_uint4(0u, 0u, 0u, 0u);
                     if (valid) {
-                        o.x = H16<HT>::pack2(v[0], v[1]);
-                        o.y = H16<HT>::pack2(v[2], v[3]);
-                        o.z = H16<HT>::pack2(v[4], v[5]);
-                        o.w = H16<HT>::pack2(v[6], v[7]);
+                        RR_PACK8(HT, o, v);
                     }
                     *reinterpret_cast<uint4*>(slot + (((4 * i2 + kq) ^ (q & 7)) << 4)) = o;
                 }
@@ -297,20 +284,10 @@ __global__ void __launch_bounds__(512, 1) k_c3pair(C3PairArgs a, int tiles_w, in
         for (int j = 0; j < FN; ++j) {
             const int p = wpx * (TP / 2) + j * 16 + r16;  // tile-local pixel
             float v[8];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                v[r] = acc[0][j][r] * sc[r] + sh[r];
-                v[4 + r] = acc[1][j][r] * sc[4 + r] + sh[4 + r];
-            }
-            if (leaky2) {
-#pragma unroll
-                for (int r = 0; r < 8; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope2;
-            }
+            RR_BN_PAIR(acc[0][j], acc[1][j], sc, sh, v);
+            if (leaky2) RR_LEAKY(8, v, a.slope2);
             uint4 o;
-            o.x = H16<HT>::pack2(v[0], v[1]);
-            o.y = H16<HT>::pack2(v[2], v[3]);
-            o.z = H16<HT>::pack2(v[4], v[5]);
-            o.w = H16<HT>::pack2(v[6], v[7]);
+            RR_PACK8(HT, o, v);
             *reinterpret_cast<uint4*>(sT2 + p * 128 + (((4 * wc + kq) ^ (p & 7)) << 4)) = o;
         }
     };
@@ -383,11 +360,7 @@ __global__ void __launch_bounds__(512, 1) k_c3pair(C3PairArgs a, int tiles_w, in
                 const int i2 = i0 + g;
                 const int c = 32 * i2 + 8 * kq;
                 float v[8];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v[r] = acc3[g][0][r] * sS3[c + r] + sH3[c + r];
-                    v[4 + r] = acc3[g][1][r] * sS3[c + 4 + r] + sH3[c + 4 + r];
-                }
+                RR_BN_PAIR(acc3[g][0], acc3[g][1], sS3 + c, sH3 + c, v);
                 if constexpr (PROJ) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
@@ -396,27 +369,15 @@ __global__ void __launch_bounds__(512, 1) k_c3pair(C3PairArgs a, int tiles_w, in
                     }
                 } else {
                     const uint4 qv = rv[i2];
-                    const unsigned w4[4] = {qv.x, qv.y, qv.z, qv.w};
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        v[2 * r] += H16<HT>::lo(w4[r]);
-                        v[2 * r + 1] += H16<HT>::hi(w4[r]);
-                    }
+                    RR_ADD_PACKED8(HT, qv, v);
                 }
-                if (leaky3) {
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope3;
-                }
-                yq[i2].x = H16<HT>::pack2(v[0], v[1]);
-                yq[i2].y = H16<HT>::pack2(v[2], v[3]);
-                yq[i2].z = H16<HT>::pack2(v[4], v[5]);
-                yq[i2].w = H16<HT>::pack2(v[6], v[7]);
+                if (leaky3) RR_LEAKY(8, v, a.slope3);
+                RR_PACK8(HT, yq[i2], v);
                 st16_once(a.y + p * C3 + c, yq[i2]);
             }
         }
         f32x4_t zacc[NF1];
-#pragma unroll
-        for (int o = 0; o < NF1; ++o) zacc[o] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+        RR_ZERO(1, zacc);
 #pragma unroll
         for (int kk = 0; kk < NK1; ++kk) {
             int abase = 0;
@@ -431,20 +392,10 @@ __global__ void __launch_bounds__(512, 1) k_c3pair(C3PairArgs a, int tiles_w, in
         for (int o2 = 0; o2 < NF1 / 2; ++o2) {
             const int c = 32 * o2 + 8 * kq;
             float v[8];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                v[r] = zacc[2 * o2][r] * sS1[c + r] + sH1[c + r];
-                v[4 + r] = zacc[2 * o2 + 1][r] * sS1[c + 4 + r] + sH1[c + 4 + r];
-            }
-            if (leaky1) {
-#pragma unroll
-                for (int r = 0; r < 8; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope1;
-            }
+            RR_BN_PAIR(zacc[2 * o2], zacc[2 * o2 + 1], sS1 + c, sH1 + c, v);
+            if (leaky1) RR_LEAKY(8, v, a.slope1);
             uint4 o;
-            o.x = H16<HT>::pack2(v[0], v[1]);
-            o.y = H16<HT>::pack2(v[2], v[3]);
-            o.z = H16<HT>::pack2(v[4], v[5]);
-            o.w = H16<HT>::pack2(v[6], v[7]);
+            RR_PACK8(HT, o, v);
             st16_once(a.z + p * C1 + c, o);
         }
     };

@@ -24,6 +24,7 @@
 // of the kNN (scripts/test.py:247).
 #include "rr_internal.h"
 #include "rr_ldsdma.h"
+#include "rr_epilogue.h"
 
 #include <cstdlib>
 
@@ -124,10 +125,7 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
     };
 
     f32x4_t acc[FM][FN];
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    RR_ZERO(2, acc);
 
     const int nk = a.kp / BK;
     const int r16 = lane & 15, kq = lane >> 4;
@@ -230,10 +228,7 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] += rv[r];
                 }
-                if (leaky) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope;
-                }
+                if (leaky) RR_LEAKY(4, v, a.slope);
                 St4<TO>::st(Y + o, v);
             } else {
                 for (int r = 0; r < 4; ++r) {

@@ -28,6 +28,7 @@
 // leaky_relu (cirtorch/utils/misc.py:175-235).
 #include "rr_internal.h"
 #include "rr_ldsdma.h"
+#include "rr_epilogue.h"
 #include "rr_tilewalk.h"
 
 #include <type_traits>
@@ -127,10 +128,7 @@ __global__ void __launch_bounds__(64 * WC * WP) k_conv3x3(ConvArgs a, int tiles_
     }
 
     f32x4_t acc[FM][FN];
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    RR_ZERO(2, acc);
 
     // A / B fragments of half-step hs (channels 32*hs .. +31 of the 64-channel
     // K-step) at tap offset toff, and the FM x FN MFMAs on them
@@ -173,20 +171,10 @@ __global__ void __launch_bounds__(64 * WC * WP) k_conv3x3(ConvArgs a, int tiles_
         const int p = wp * (TP / WP) + j * 16 + r16;
         const long long pix = ((long long)tc.img * H + tc.oh0 + p / TW) * W + tc.ow0 + p % TW;
         float v[8];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            v[r] = ac[2 * i2][j][r] * sc[r] + sh[r];
-            v[4 + r] = ac[2 * i2 + 1][j][r] * sc[4 + r] + sh[4 + r];
-        }
-        if (leaky) {
-#pragma unroll
-            for (int r = 0; r < 8; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * slope;
-        }
+        RR_BN_PAIR(ac[2 * i2][j], ac[2 * i2 + 1][j], sc, sh, v);
+        if (leaky) RR_LEAKY(8, v, slope);
         uint4 o;
-        o.x = H16<HT>::pack2(v[0], v[1]);
-        o.y = H16<HT>::pack2(v[2], v[3]);
-        o.z = H16<HT>::pack2(v[4], v[5]);
-        o.w = H16<HT>::pack2(v[6], v[7]);
+        RR_PACK8(HT, o, v);
         *reinterpret_cast<uint4*>(Y + pix * a.ldy + c) = o;
     };
     auto load_affine = [&](int ct, int i2, float (&sc)[8], float (&sh)[8]) {
@@ -208,10 +196,7 @@ __global__ void __launch_bounds__(64 * WC * WP) k_conv3x3(ConvArgs a, int tiles_
 #pragma unroll
             for (int j = 0; j < FN; ++j) store_one(tc, acc, i2, j, sc, sh);
         }
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-            for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+        RR_ZERO(2, acc);
     };
 
     TileC cur = tile_of(0);
@@ -237,18 +222,11 @@ __global__ void __launch_bounds__(64 * WC * WP) k_conv3x3(ConvArgs a, int tiles_
                 const int p = wp * (TP / WP) + j * 16 + r16;
                 const long long pix = ((long long)tc.img * H + tc.oh0 + p / TW) * W + tc.ow0 + p % TW;
                 float v[8];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v[r] = accP[2 * i2][j][r] * esc[i2][r] + esh[i2][r];
-                    v[4 + r] = accP[2 * i2 + 1][j][r] * esc[i2][4 + r] + esh[i2][4 + r];
-                }
+                RR_BN_PAIR(accP[2 * i2][j], accP[2 * i2 + 1][j], esc[i2], esh[i2], v);
 #pragma unroll
                 for (int r = 0; r < 8; ++r) v[r] = fmaxf(v[r], v[r] * sl);
                 uint4 o;
-                o.x = H16<HT>::pack2(v[0], v[1]);
-                o.y = H16<HT>::pack2(v[2], v[3]);
-                o.z = H16<HT>::pack2(v[4], v[5]);
-                o.w = H16<HT>::pack2(v[6], v[7]);
+                RR_PACK8(HT, o, v);
                 *reinterpret_cast<uint4*>(Y + pix * a.ldy + c) = o;
             };
             TileC prev = cur;
@@ -510,10 +488,7 @@ __global__ void __launch_bounds__(512, 1) k_c3w64(ConvArgs a, int tiles_w, int t
                     base[j][dx][hs] = Ps + r;
                 }
         f32x4_t acc[2][FN];
-#pragma unroll
-        for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-            for (int j = 0; j < FN; ++j) acc[ii][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+        RR_ZERO(2, acc);
 #pragma unroll
         for (int s = 0; s < 18; ++s) {
             const int tap = s >> 1, hs = s & 1, dy = tap / 3, dx = tap % 3;
@@ -538,20 +513,10 @@ __global__ void __launch_bounds__(512, 1) k_c3w64(ConvArgs a, int tiles_w, int t
             const int p = wp * (TP / 4) + j * 16 + r16;
             const long long pix = ((long long)img * H + oh0 + p / TW) * W + ow0 + p % TW;
             float v[8];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                v[r] = acc[0][j][r] * sc[r] + sh[r];
-                v[4 + r] = acc[1][j][r] * sc[4 + r] + sh[4 + r];
-            }
-            if (leaky) {
-#pragma unroll
-                for (int r = 0; r < 8; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * slope;
-            }
+            RR_BN_PAIR(acc[0][j], acc[1][j], sc, sh, v);
+            if (leaky) RR_LEAKY(8, v, slope);
             uint4 o;
-            o.x = H16<HT>::pack2(v[0], v[1]);
-            o.y = H16<HT>::pack2(v[2], v[3]);
-            o.z = H16<HT>::pack2(v[4], v[5]);
-            o.w = H16<HT>::pack2(v[6], v[7]);
+            RR_PACK8(HT, o, v);
             *reinterpret_cast<uint4*>(Y + pix * a.ldy + c) = o;
         }
     }

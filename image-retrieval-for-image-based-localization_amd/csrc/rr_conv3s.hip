@@ -38,6 +38,7 @@
 // misc.py:166-172) + the ABN eval BN + leaky_relu (cirtorch/utils/misc.py:175-235).
 #include "rr_internal.h"
 #include "rr_ldsdma.h"
+#include "rr_epilogue.h"
 #include "rr_tilewalk.h"
 
 namespace rr {
@@ -74,19 +75,12 @@ template <typename HT>
 __device__ __forceinline__ void store8(HT* __restrict__ Y, long long o, const f32x4_t& a0, const f32x4_t& a1,
                                        const float (&sc)[8], const float (&sh)[8], float sl) {
     float v[8];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        v[r] = a0[r] * sc[r] + sh[r];
-        v[4 + r] = a1[r] * sc[4 + r] + sh[4 + r];
-    }
+    RR_BN_PAIR(a0, a1, sc, sh, v);
     // leaky(v) = max(v, slope * v) for slope in [0, 1] (host-checked; identity: slope 1)
 #pragma unroll
     for (int r = 0; r < 8; ++r) v[r] = fmaxf(v[r], v[r] * sl);
     uint4 q;
-    q.x = H16<HT>::pack2(v[0], v[1]);
-    q.y = H16<HT>::pack2(v[2], v[3]);
-    q.z = H16<HT>::pack2(v[4], v[5]);
-    q.w = H16<HT>::pack2(v[6], v[7]);
+    RR_PACK8(HT, q, v);
     *reinterpret_cast<uint4*>(Y + o) = q;
 }
 

@@ -18,6 +18,7 @@
 //     (never __syncthreads(), whose fence would drain the prefetch).
 #include "rr_internal.h"
 #include "rr_ldsdma.h"
+#include "rr_epilogue.h"
 #include "rr_tilewalk.h"
 
 #include <cstdlib>
@@ -29,6 +30,46 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
 
 __device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
+
+// The im2col row descriptor (p -> image, oh, ow -> b_hi, b_wi, b_base), the 8-phase kernels' K-step
+// descriptor (KD / kdesc) with its operand-B offset, and the natural-order and score stores stay
+// written out in each kernel: shared as forced-inline functions, each of them changed the
+// instructions or register counts of the kernels that used it (tools/isa_diff.py).
+
+// One MFMA on 8 packed 16-bit values per lane, or (T = int8_t) 16 int8 with exact int32 sums
+// kept in the float accumulator's registers.
+__device__ __forceinline__ f32x4_t mfma_i8(uint4 a, uint4 b, f32x4_t c) {
+    return __builtin_bit_cast(f32x4_t, __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4_t, a),
+                                                                             __builtin_bit_cast(i32x4_t, b),
+                                                                             __builtin_bit_cast(i32x4_t, c), 0, 0, 0));
+}
+template <typename T>
+__device__ __forceinline__ f32x4_t mfma_t(uint4 a, uint4 b, f32x4_t c) {
+    if constexpr (std::is_same<T, int8_t>::value) return mfma_i8(a, b, c);
+    else return H16<T>::mfma(a, b, c);
+}
+// Fragments of the LDS-ring 8-phase kernels: N 16-row fragments x 2 32-deep halves from rows
+// row0 + 16 i + r16 of the half-tile at base (A: N = 4, row0 = 64 grp; B: N = 2, row0 = 32 wn);
+// r16 and kq are the kernel's.  Macros for RR_ZERO's reason (rr_epilogue.h) ...
+#define RR_READ_FRAG(f, N, base, row0)                                                                              \
+    do {                                                                                                            \
+        const char* base_ = (base);                                                                                 \
+        _Pragma("unroll") for (int i_ = 0; i_ < (N); ++i_)                                                          \
+            _Pragma("unroll") for (int hs_ = 0; hs_ < 2; ++hs_)                                                     \
+                (f)[i_][hs_] = *reinterpret_cast<const uint4*>(base_ + swz((row0) + i_ * 16 + r16, kq + 4 * hs_)); \
+    } while (0)
+// ... and a phase's 16 MFMAs on them, one 64 x 32 sub-block of a quadrant
+#define RR_MFMA_16(T, fa, fb, acc)                                                                          \
+    do {                                                                                                    \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
+        __builtin_amdgcn_s_setprio(1);                                                                      \
+        _Pragma("unroll") for (int hs_ = 0; hs_ < 2; ++hs_)                                                 \
+            _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                \
+                _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_)                                            \
+                    (acc)[i_][j_] = mfma_t<T>((fa)[i_][hs_], (fb)[j_][hs_], (acc)[i_][j_]);                 \
+        __builtin_amdgcn_s_setprio(0);                                                                      \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
+    } while (0)
 
 // Persistent tile loop: block b walks tiles t = b, b + grid, ... as one
 // flattened stream of (tile, K-step) steps, so the LDS-DMA of the next tile's
@@ -188,10 +229,7 @@ __global__ void __launch_bounds__(64 * WC * WP, ((NS == 2 && AK * TC <= 256) || 
     };
 
     f32x4_t acc[FM][FN];
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    RR_ZERO(2, acc);
 
     const int r16 = lane & 15, kq = lane >> 4;
     const int arow0 = wc * (TC / WC) + r16, brow0 = wp * (TP / WP) + r16;
@@ -238,10 +276,8 @@ __global__ void __launch_bounds__(64 * WC * WP, ((NS == 2 && AK * TC <= 256) || 
             for (int i2 = 0; i2 < FM / 2; ++i2) {
                 const int c = min(c0 + wc * (TC / WC) + 32 * i2 + 8 * kq, a.cout - 8);
                 if (affine) {
-                    St4<float>::ld(a.scale + c, sc[i2]);
-                    St4<float>::ld(a.scale + c + 4, sc[i2] + 4);
-                    St4<float>::ld(a.shift + c, sh[i2]);
-                    St4<float>::ld(a.shift + c + 4, sh[i2] + 4);
+                    ld8<float>(a.scale + c, sc[i2]);
+                    ld8<float>(a.shift + c, sh[i2]);
                 } else {
 #pragma unroll
                     for (int r = 0; r < 8; ++r) { sc[i2][r] = 1.f; sh[i2][r] = 0.f; }
@@ -256,39 +292,22 @@ __global__ void __launch_bounds__(64 * WC * WP, ((NS == 2 && AK * TC <= 256) || 
                     const int p = p0 + wp * (TP / WP) + j * 16 + r16;
                     if (p >= a.P) continue;
                     float v[8];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        v[r] = acc[2 * i2][j][r] * sc[i2][r] + sh[i2][r];
-                        v[4 + r] = acc[2 * i2 + 1][j][r] * sc[i2][4 + r] + sh[i2][4 + r];
-                    }
+                    RR_BN_PAIR(acc[2 * i2][j], acc[2 * i2 + 1][j], sc[i2], sh[i2], v);
                     const long long o = (long long)p * a.ldy + c;
                     if (resid) {
                         float rv[8];
                         if constexpr (PREF) {
-                            const uint4 q = rres[BUF][i2][j];
-                            const unsigned w4[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                rv[2 * r] = H16<TO>::lo(w4[r]);
-                                rv[2 * r + 1] = H16<TO>::hi(w4[r]);
-                            }
+                            RR_UNPACK8(TO, rres[BUF][i2][j], rv);
                         } else {
                             St4<TO>::ld(R + o, rv);
                             St4<TO>::ld(R + o + 4, rv + 4);
                         }
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) v[r] += rv[r];
+                        RR_ADD8(v, rv);
                     }
-                    if (leaky) {
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope;
-                    }
+                    if (leaky) RR_LEAKY(8, v, a.slope);
                     if constexpr (sizeof(TO) == 2) {
                         uint4 q;
-                        q.x = H16<TO>::pack2(v[0], v[1]);
-                        q.y = H16<TO>::pack2(v[2], v[3]);
-                        q.z = H16<TO>::pack2(v[4], v[5]);
-                        q.w = H16<TO>::pack2(v[6], v[7]);
+                        RR_PACK8(TO, q, v);
                         *reinterpret_cast<uint4*>(Y + o) = q;
                     } else {
                         St4<TO>::st(Y + o, v);
@@ -403,6 +422,7 @@ __global__ void __launch_bounds__(64 * WC * WP, ((NS == 2 && AK * TC <= 256) || 
             for (int i = 0; i < FM; ++i) fa[i] = *reinterpret_cast<const uint4*>(As + swz(arow0 + i * 16, kq + 4 * hs));
 #pragma unroll
             for (int j = 0; j < FN; ++j) fb[j] = *reinterpret_cast<const uint4*>(Bs + swz(brow0 + j * 16, kq + 4 * hs));
+            // (builtins written out, here and in k_gemm8s: through H16<T>::mfma these kernels' register allocation changes)
             if constexpr (std::is_same<T, f16_t>::value) {
 #pragma unroll
                 for (int i = 0; i < FM; ++i)
@@ -442,14 +462,23 @@ __global__ void __launch_bounds__(64 * WC * WP, ((NS == 2 && AK * TC <= 256) || 
             } else {
                 epilogue(B0{}, t);
             }
-#pragma unroll
-            for (int i = 0; i < FM; ++i)
-#pragma unroll
-                for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+            RR_ZERO(2, acc);
             ck = 0;
             ++ctile;
         }
     }
+}
+
+// Operand-B addressing of a conv with esz-byte elements (the kernels' KM): 1 = 1x1 / pad 0,
+// 2 = tap-uniform im2col (c_in a multiple of the 128-B K-step, every K-step index in the magic
+// multiply's range), 0 = generic im2col.
+static int operand_b_mode(const ConvArgs& a, bool k1, int esz) {
+    return k1 ? 1 : ((a.cin * esz) % 128 == 0 && tapu_ok(a.kh * a.kw, (long long)a.kp * esz / 128)) ? 2 : 0;
+}
+// The kernels' LDS-DMA offsets are 32-bit with bit 31 = OOB: operand B (b_elems elements) and
+// one tile's a_rows weight rows of kp elements must each stay below 2^31 bytes.
+static bool offsets_fit31(long long b_elems, int a_rows, int kp, int esz) {
+    return b_elems * esz < (1ll << 31) && (long long)a_rows * kp * esz < (1ll << 31);
 }
 
 // k_igemm's xmap argument: bit 0 RR_TUNE_GEMM_XCD_MAP, bit 1 RR_GEMM_PRIO=1
@@ -467,7 +496,7 @@ static void launch_ns(const ConvArgs& a, bool k1, bool perm, hipStream_t s) {
     const int ntiles = tiles_p * tiles_c;
     const int cap = PER_CU * grid_cus();
     const int grid = ntiles < cap ? ntiles : cap;
-    const int km = k1 ? 1 : ((a.cin * (int)sizeof(T)) % 128 == 0 && tapu_ok(a.kh * a.kw, (long long)a.kp * (int)sizeof(T) / 128)) ? 2 : 0;
+    const int km = operand_b_mode(a, k1, (int)sizeof(T));
 #define RR_L3(PV)                                                                                                    \
     do {                                                                                                             \
         if (km == 1)                                                                                                 \
@@ -669,52 +698,13 @@ __global__ void __launch_bounds__(512, 1) k_gemm8(ConvArgs a, int tiles_p, int n
     const KD kd0 = kdesc(0), kd1 = kdesc(1);
 
     f32x4_t acc[2][2][4][2];
-#pragma unroll
-    for (int qa = 0; qa < 2; ++qa)
-#pragma unroll
-        for (int qb = 0; qb < 2; ++qb)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[qa][qb][i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    RR_ZERO(4, acc);
 
     const int r16 = lane & 15, kq = lane >> 4;
     uint4 fa[4][2], fb[2][2];
-    auto read_a = [&](int buf, int h) {
-        const char* base = smem + (buf * 4 + h) * HT;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int hs = 0; hs < 2; ++hs)
-                fa[i][hs] = *reinterpret_cast<const uint4*>(base + swz(grp * 64 + i * 16 + r16, kq + 4 * hs));
-    };
-    auto read_b = [&](int buf, int h) {
-        const char* base = smem + (buf * 4 + 2 + h) * HT;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int hs = 0; hs < 2; ++hs)
-                fb[j][hs] = *reinterpret_cast<const uint4*>(base + swz(wn * 32 + j * 16 + r16, kq + 4 * hs));
-    };
-    auto mfma_q = [&](int qa, int qb) {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int hs = 0; hs < 2; ++hs)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    if constexpr (I8)
-                        acc[qa][qb][i][j] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_mfma_i32_16x16x64_i8(
-                            __builtin_bit_cast(i32x4_t, fa[i][hs]), __builtin_bit_cast(i32x4_t, fb[j][hs]),
-                            __builtin_bit_cast(i32x4_t, acc[qa][qb][i][j]), 0, 0, 0));
-                    else
-                        acc[qa][qb][i][j] = H16<T>::mfma(fa[i][hs], fb[j][hs], acc[qa][qb][i][j]);
-                }
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-    };
+    auto read_a = [&](int buf, int h) { RR_READ_FRAG(fa, 4, smem + (buf * 4 + h) * HT, grp * 64); };
+    auto read_b = [&](int buf, int h) { RR_READ_FRAG(fb, 2, smem + (buf * 4 + 2 + h) * HT, wn * 32); };
+    auto mfma_q = [&](int qa, int qb) { RR_MFMA_16(T, fa, fb, acc[qa][qb]); };
 
     // ---- prologue: K-step 0 into E (A0 B1 A1 B0), K-step 1's A0 / B1 into O
     auto prologue = [&]() {
@@ -827,10 +817,8 @@ __global__ void __launch_bounds__(512, 1) k_gemm8(ConvArgs a, int tiles_p, int n
 #pragma unroll
                     for (int r = 0; r < 8; ++r) { sc[r] = lds_sc[c + r]; sh[r] = lds_sh[c + r]; }
                 } else if (affine) {
-                    St4<float>::ld(a.scale + c, sc);
-                    St4<float>::ld(a.scale + c + 4, sc + 4);
-                    St4<float>::ld(a.shift + c, sh);
-                    St4<float>::ld(a.shift + c + 4, sh + 4);
+                    ld8<float>(a.scale + c, sc);
+                    ld8<float>(a.shift + c, sh);
                 } else {
 #pragma unroll
                     for (int r = 0; r < 8; ++r) { sc[r] = 1.f; sh[r] = 0.f; }
@@ -842,29 +830,18 @@ __global__ void __launch_bounds__(512, 1) k_gemm8(ConvArgs a, int tiles_p, int n
                         const int p = ep0 + qb * 128 + wn * 32 + j * 16 + r16;
                         if (p >= a.P) continue;
                         float v[8];
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            v[r] = acc[qa][qb][2 * i2][j][r] * sc[r] + sh[r];
-                            v[4 + r] = acc[qa][qb][2 * i2 + 1][j][r] * sc[4 + r] + sh[4 + r];
-                        }
+                        RR_BN_PAIR(acc[qa][qb][2 * i2][j], acc[qa][qb][2 * i2 + 1][j], sc, sh, v);
                         const long long o = (long long)p * a.ldy + c;
                         if (resid) {
                             float rv[8];
                             St4<TO>::ld(R + o, rv);
                             St4<TO>::ld(R + o + 4, rv + 4);
-#pragma unroll
-                            for (int r = 0; r < 8; ++r) v[r] += rv[r];
+                            RR_ADD8(v, rv);
                         }
-                        if (leaky) {
-#pragma unroll
-                            for (int r = 0; r < 8; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope;
-                        }
+                        if (leaky) RR_LEAKY(8, v, a.slope);
                         if constexpr (sizeof(TO) == 2) {
                             uint4 q;
-                            q.x = H16<TO>::pack2(v[0], v[1]);
-                            q.y = H16<TO>::pack2(v[2], v[3]);
-                            q.z = H16<TO>::pack2(v[4], v[5]);
-                            q.w = H16<TO>::pack2(v[6], v[7]);
+                            RR_PACK8(TO, q, v);
                             *reinterpret_cast<uint4*>(Y + o) = q;
                         } else {
                             St4<TO>::st(Y + o, v);
@@ -926,14 +903,7 @@ __global__ void __launch_bounds__(512, 1) k_gemm8(ConvArgs a, int tiles_p, int n
             }
         }
     }
-#pragma unroll
-    for (int qa = 0; qa < 2; ++qa)
-#pragma unroll
-        for (int qb = 0; qb < 2; ++qb)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[qa][qb][i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    RR_ZERO(4, acc);
     if (!more) break;
     }  // persistent tile loop
 }
@@ -996,51 +966,12 @@ __global__ void __launch_bounds__(512, 1) k_gemm8h(ConvArgs a, int ntiles) {
     };
 
     f32x4_t acc[2][4][2];
-#pragma unroll
-    for (int qa = 0; qa < 2; ++qa)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc[qa][i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    RR_ZERO(3, acc);
     const int r16 = lane & 15, kq = lane >> 4;
     uint4 fa[4][2], fb[2][2];
-    auto read_a = [&](int kt, int h) {
-        const char* base = smem + (kt % 3) * ST + h * HT;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int hs = 0; hs < 2; ++hs)
-                fa[i][hs] = *reinterpret_cast<const uint4*>(base + swz(grp * 64 + i * 16 + r16, kq + 4 * hs));
-    };
-    auto read_b = [&](int kt) {
-        const char* base = smem + (kt % 3) * ST + 2 * HT;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int hs = 0; hs < 2; ++hs)
-                fb[j][hs] = *reinterpret_cast<const uint4*>(base + swz(wn * 32 + j * 16 + r16, kq + 4 * hs));
-    };
-    auto mfma_q = [&](int qa) {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int hs = 0; hs < 2; ++hs)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    if constexpr (std::is_same<T, f16_t>::value)
-                        acc[qa][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                            __builtin_bit_cast(f16x8_t, fa[i][hs]), __builtin_bit_cast(f16x8_t, fb[j][hs]),
-                            acc[qa][i][j], 0, 0, 0);
-                    else
-                        acc[qa][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                            __builtin_bit_cast(bf16x8_t, fa[i][hs]), __builtin_bit_cast(bf16x8_t, fb[j][hs]),
-                            acc[qa][i][j], 0, 0, 0);
-                }
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-    };
+    auto read_a = [&](int kt, int h) { RR_READ_FRAG(fa, 4, smem + (kt % 3) * ST + h * HT, grp * 64); };
+    auto read_b = [&](int kt) { RR_READ_FRAG(fb, 2, smem + (kt % 3) * ST + 2 * HT, wn * 32); };
+    auto mfma_q = [&](int qa) { RR_MFMA_16(T, fa, fb, acc[qa]); };
 
     // prologue: K-steps 0 and 1 (A0, B0, A1 each); K-step 0's A0 / B0 landed
     issue(0, 0); issue(2, 0); issue(1, 0);
@@ -1185,10 +1116,7 @@ __global__ void __launch_bounds__(512, 1) k_gemm8s(ConvArgs a, int ntiles) {
     for (int u = 0; u < R; ++u) issue(ar[u]);
 
     f32x4_t acc[2][8];
-#pragma unroll
-    for (int g = 0; g < 2; ++g)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[g][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    RR_ZERO(2, acc);
     int cst = 0;     // query stage of the position being consumed
     int m = 0, kc = 0;
     for (int f0 = 0; f0 < F; f0 += R) {
@@ -1268,10 +1196,7 @@ __global__ void __launch_bounds__(512, 1) k_gemm8s(ConvArgs a, int ntiles) {
                         }
                     }
                 }
-#pragma unroll
-                for (int g = 0; g < 2; ++g)
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) acc[g][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+                RR_ZERO(2, acc);
                 kc = 0;
                 ++m;
             }
@@ -1410,50 +1335,11 @@ __global__ void __launch_bounds__(512, 1) k_gemm8a(ConvArgs a, int tiles_p, int 
     };
 
     f32x4_t acc[2][4][2];
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc[qb][i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    RR_ZERO(3, acc);
     uint4 fa[4][2], fb[2][2];
-    auto read_a = [&](int kt) {
-        const char* base = smem + (kt % 3) * ST;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int hs = 0; hs < 2; ++hs)
-                fa[i][hs] = *reinterpret_cast<const uint4*>(base + swz(grp * 64 + i * 16 + r16, kq + 4 * hs));
-    };
-    auto read_b = [&](int kt, int h) {
-        const char* base = smem + (kt % 3) * ST + (1 + h) * HT;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int hs = 0; hs < 2; ++hs)
-                fb[j][hs] = *reinterpret_cast<const uint4*>(base + swz(wn * 32 + j * 16 + r16, kq + 4 * hs));
-    };
-    auto mfma_q = [&](int qb) {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int hs = 0; hs < 2; ++hs)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    if constexpr (std::is_same<T, f16_t>::value)
-                        acc[qb][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                            __builtin_bit_cast(f16x8_t, fa[i][hs]), __builtin_bit_cast(f16x8_t, fb[j][hs]),
-                            acc[qb][i][j], 0, 0, 0);
-                    else
-                        acc[qb][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                            __builtin_bit_cast(bf16x8_t, fa[i][hs]), __builtin_bit_cast(bf16x8_t, fb[j][hs]),
-                            acc[qb][i][j], 0, 0, 0);
-                }
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-    };
+    auto read_a = [&](int kt) { RR_READ_FRAG(fa, 4, smem + (kt % 3) * ST, grp * 64); };
+    auto read_b = [&](int kt, int h) { RR_READ_FRAG(fb, 2, smem + (kt % 3) * ST + (1 + h) * HT, wn * 32); };
+    auto mfma_q = [&](int qb) { RR_MFMA_16(T, fa, fb, acc[qb]); };
     auto prologue = [&]() {
         const KD d0 = kdesc(0), d1 = kdesc(1);
         issue(0, d0); issue(1, d0); issue(2, d0);
@@ -1514,38 +1400,22 @@ __global__ void __launch_bounds__(512, 1) k_gemm8a(ConvArgs a, int tiles_p, int 
                     const int p = ep0 + qb * 128 + wn * 32 + j * 16 + r16;
                     if (p >= a.P) continue;
                     float v[8];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        v[r] = acc[qb][2 * i2][j][r] * esc[i2][r] + esh[i2][r];
-                        v[4 + r] = acc[qb][2 * i2 + 1][j][r] * esc[i2][4 + r] + esh[i2][4 + r];
-                    }
+                    RR_BN_PAIR(acc[qb][2 * i2][j], acc[qb][2 * i2 + 1][j], esc[i2], esh[i2], v);
                     const long long o = (long long)p * a.ldy + c;
                     if (resid) {
                         float rv[8];
                         St4<T>::ld(R + o, rv);
                         St4<T>::ld(R + o + 4, rv + 4);
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) v[r] += rv[r];
+                        RR_ADD8(v, rv);
                     }
-                    if (leaky) {
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope;
-                    }
+                    if (leaky) RR_LEAKY(8, v, a.slope);
                     uint4 q;
-                    q.x = H16<T>::pack2(v[0], v[1]);
-                    q.y = H16<T>::pack2(v[2], v[3]);
-                    q.z = H16<T>::pack2(v[4], v[5]);
-                    q.w = H16<T>::pack2(v[6], v[7]);
+                    RR_PACK8(T, q, v);
                     *reinterpret_cast<uint4*>(Y + o) = q;
                 }
         }
         if (!more) break;
-#pragma unroll
-        for (int qb = 0; qb < 2; ++qb)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[qb][i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+        RR_ZERO(3, acc);
     }
     vm_wait<0>();
 }
@@ -1556,10 +1426,10 @@ __global__ void __launch_bounds__(512, 1) k_gemm8a(ConvArgs a, int tiles_p, int 
 // half the MFMAs).
 bool gemm8_eligible(const ConvArgs& a, bool k1, int esz) {
     if (!g_tune.gemm8_mode() || esz != 2) return false;
-    const int km = k1 ? 1 : ((a.cin * 2) % 128 == 0 && tapu_ok(a.kh * a.kw, a.kp / 64)) ? 2 : 0;
+    const int km = operand_b_mode(a, k1, 2);
     const int nk = a.kp / 64;
     if (km == 0 || nk < 2 || (nk & 1) || a.kp % 64) return false;
-    if ((long long)a.n * a.h * a.w_ * a.cin * 2 >= (1ll << 31) || 256ll * a.kp * 2 >= (1ll << 31)) return false;
+    if (!offsets_fit31((long long)a.n * a.h * a.w_ * a.cin, 256, a.kp, 2)) return false;
     if ((a.flags & RR_CONV_PERM32) && a.cout % 32) return false;
     const long long ntiles = (long long)((a.P + 255) / 256) * ((a.cout + 255) / 256);
     // (a partial last channel tile is negligible for long channel dims, e.g. the
@@ -1593,8 +1463,7 @@ static bool try_gemm8(const ConvArgs& a, bool k1, bool perm, hipStream_t s) {
         const bool short_k1 = g_tune.gemm8_short_persist() && k1 && a.kp / 64 <= 16 && !(a.flags & RR_CONV_RESIDUAL);
         const bool persist = !g_tune.gemm8_tile() && (g_tune.gemm8_mode() == 2 || !std::is_same<T, TO>::value ||
                                                       (std::is_same<T, TO>::value && short_k1));
-        // (a grid below 8 blocks would leave some XCD's tile range without a block)
-        const dim3 g((unsigned)(!persist || cus < 8 || ntiles < cus ? ntiles : cus)), b(512);
+        const dim3 g((unsigned)(persist ? range_walk_grid(ntiles, cus) : ntiles)), b(512);
         // conv GEMMs (16-bit out) walk their tiles pixel-major (RR_TUNE_GEMM8 | 64: channel-major)
         const int pmajor = std::is_same<T, TO>::value && g_tune.gemm8_pmajor() && tiles_c > 1;
 #define RR_G8(KMV, PV) hipLaunchKernelGGL((k_gemm8<T, TO, KMV, PV>), g, b, 0, s, a, tiles_p, (int)ntiles, pmajor)
@@ -1621,15 +1490,12 @@ static bool try_gemm8h(const ConvArgs& a, bool k1, bool perm, hipStream_t s) {
     } else {
         if (!g_tune.gemm8h() || !k1 || perm || a.kp % 64 || a.kp != a.cin || a.kp / 64 < 2) return false;
         if (a.flags & (RR_CONV_AFFINE | RR_CONV_RESIDUAL) || a.act != RR_ACT_IDENTITY) return false;
-        if (a.P < 1 || a.P > 128 || (long long)a.P * a.cin * 2 >= (1ll << 31) || 256ll * a.kp * 2 >= (1ll << 31))
-            return false;
+        if (a.P < 1 || a.P > 128 || !offsets_fit31((long long)a.P * a.cin, 256, a.kp, 2)) return false;
         const long long ntiles = ((long long)a.cout + 255) / 256;
         if (ntiles >= (1ll << 31)) return false;
         if (g_tune.gemm8s()) {
-            // persistent streaming form: one block per CU (a grid below 8 blocks
-            // would leave some XCD's tile range without a block)
-            const long long cus = grid_cus();
-            const unsigned g = (unsigned)(cus < 8 || ntiles < cus ? ntiles : cus);
+            // persistent streaming form: one block per CU
+            const unsigned g = (unsigned)range_walk_grid(ntiles, grid_cus());
             // K-steps in flight per wave: 4 (Q = 128 vs 1M rows: 1.13 / 1.12 ms vs 1.15 / 1.14 at 6,
             // 1.28 at 8, profiles/r03_ab/r03ac_gemm8s_depth_ab.txt); RR_GEMM8S_R = 3 or 6: A/B
             static const int rdepth = getenv("RR_GEMM8S_R") ? atoi(getenv("RR_GEMM8S_R")) : 4;
@@ -1650,9 +1516,8 @@ static bool try_gemm8h(const ConvArgs& a, bool k1, bool perm, hipStream_t s) {
 // tap-uniform im2col), enough 128 x 256 tiles to fill the chip twice.
 bool gemm8a_eligible(const ConvArgs& a, bool k1) {
     if (!g_tune.gemm8a() || !(a.flags & RR_CONV_PERM32) || a.cout % 128 || a.cout >= 256) return false;
-    const int km = k1 ? 1 : ((a.cin * 2) % 128 == 0 && tapu_ok(a.kh * a.kw, a.kp / 64)) ? 2 : 0;
-    if (km == 0 || a.kp % 64 || a.kp / 64 < 2) return false;
-    if ((long long)a.n * a.h * a.w_ * a.cin * 2 >= (1ll << 31) || 128ll * a.kp * 2 >= (1ll << 31)) return false;
+    if (operand_b_mode(a, k1, 2) == 0 || a.kp % 64 || a.kp / 64 < 2) return false;
+    if (!offsets_fit31((long long)a.n * a.h * a.w_ * a.cin, 128, a.kp, 2)) return false;
     const long long ntiles = (long long)((a.P + 255) / 256) * (a.cout / 128);
     return ntiles >= 2 * grid_cus() && ntiles < (1ll << 31);
 }
@@ -1666,9 +1531,7 @@ static bool try_gemm8a(const ConvArgs& a, bool k1, bool perm, hipStream_t s) {
         const int tiles_p = (a.P + 255) / 256;
         const int ntiles = tiles_p;  // c_out = 128: one channel tile
         // persistent (RR_TUNE_GEMM8 value | 128: one block per tile)
-        // (a grid below 8 blocks would leave some XCD's tile range without a block)
-        const int cus = grid_cus();
-        const int grid = g_tune.gemm8a_tile() || cus < 8 || ntiles < cus ? ntiles : cus;
+        const int grid = g_tune.gemm8a_tile() ? ntiles : (int)range_walk_grid(ntiles, grid_cus());
         if (k1) hipLaunchKernelGGL((k_gemm8a<T, 1>), dim3(grid), dim3(512), 0, s, a, tiles_p, ntiles);
         else hipLaunchKernelGGL((k_gemm8a<T, 2>), dim3(grid), dim3(512), 0, s, a, tiles_p, ntiles);
         return true;
@@ -1679,13 +1542,12 @@ static bool try_gemm8a(const ConvArgs& a, bool k1, bool perm, hipStream_t s) {
 // k_gemm8s at <= 128 queries (streaming the database), persistent k_gemm8 above.
 // Needs 128-B K-steps (d % 128 == 0) and, for k_gemm8, an even K-step count.
 int gemm_scores_i8(const ConvArgs& a, hipStream_t s) {
-    if (a.kp != a.cin || a.kp % 128 || a.P < 1 || (long long)a.P * a.cin >= (1ll << 31) ||
-        256ll * a.kp >= (1ll << 31))
+    if (a.kp != a.cin || a.kp % 128 || a.P < 1 || !offsets_fit31((long long)a.P * a.cin, 256, a.kp, 1))
         return fail(RR_EINVAL, "int8 score GEMM: d must be a multiple of 128 (rows and queries below 2 GiB)");
     const long long cus = grid_cus();
     if (a.P <= 128) {
         const long long ntiles = ((long long)a.cout + 255) / 256;
-        const unsigned g = (unsigned)(cus < 8 || ntiles < cus ? ntiles : cus);
+        const unsigned g = (unsigned)range_walk_grid(ntiles, cus);
         hipLaunchKernelGGL((k_gemm8s<int8_t, 4>), dim3(g), dim3(512), 0, s, a, (int)ntiles);
         return RR_OK;
     }
@@ -1693,7 +1555,7 @@ int gemm_scores_i8(const ConvArgs& a, hipStream_t s) {
     const int tiles_p = (a.P + 255) / 256;
     const long long ntiles = (long long)tiles_p * ((a.cout + 255) / 256);
     if (ntiles >= (1ll << 31)) return fail(RR_EINVAL, "int8 score GEMM: too many tiles");
-    const dim3 g((unsigned)(cus < 8 || ntiles < cus ? ntiles : cus));
+    const dim3 g((unsigned)range_walk_grid(ntiles, cus));
     hipLaunchKernelGGL((k_gemm8<int8_t, float, 1, false>), g, dim3(512), 0, s, a, tiles_p, (int)ntiles, 0);
     return RR_OK;
 }

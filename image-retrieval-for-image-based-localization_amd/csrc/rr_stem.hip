@@ -45,6 +45,7 @@
 // bit for bit, S2dPatch sums the same products in another order.
 #include "rr_internal.h"
 #include "rr_ldsdma.h"
+#include "rr_epilogue.h"
 
 #include <type_traits>
 
@@ -252,8 +253,7 @@ __global__ void __launch_bounds__(NT) k_stem_pool(StemArgs a, TAB rt, int tiles_
             const int sr = nn / SC, sc = nn - sr * SC;
             const char* pb = patch + ((2 * sr) * IC + 2 * sc + 2 * q) * 8;
             f32x4_t acc[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+            RR_ZERO(1, acc);
 #pragma unroll
             for (int m = 0; m < 7; ++m) {
                 const uint4 b = *reinterpret_cast<const uint4*>(pb + m * IC * 8);
@@ -267,6 +267,7 @@ __global__ void __launch_bounds__(NT) k_stem_pool(StemArgs a, TAB rt, int tiles_
                 for (int i2 = 0; i2 < 2; ++i2) {
                     const int cl = 32 * i2 + 8 * q;  // 8 consecutive channels (PERM32 rows)
                     float v[8];
+                    // (written out: RR_BN_PAIR on sS + cl changes the <4, 32> kernels' loop code)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         v[r] = acc[2 * i2][r] * sS[cl + r] + sH[cl + r];
@@ -494,18 +495,11 @@ __global__ void __launch_bounds__(NT) k_stem_pool2(StemArgs a, int tiles_w, int 
                 for (int i2 = 0; i2 < 2; ++i2) {
                     const int cl = 32 * i2 + 8 * q;  // 8 consecutive channels (PERM32 rows)
                     float v[8];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        v[r] = hv[2 * i2][r] * sS[cl + r] + sH[cl + r];
-                        v[4 + r] = hv[2 * i2 + 1][r] * sS[cl + 4 + r] + sH[cl + 4 + r];
-                    }
+                    RR_BN_PAIR(hv[2 * i2], hv[2 * i2 + 1], sS + cl, sH + cl, v);
 #pragma unroll
                     for (int r = 0; r < 8; ++r) v[r] = fmaxf(v[r], v[r] * slope);
                     uint4 o;
-                    o.x = H16<HT>::pack2(v[0], v[1]);
-                    o.y = H16<HT>::pack2(v[2], v[3]);
-                    o.z = H16<HT>::pack2(v[4], v[5]);
-                    o.w = H16<HT>::pack2(v[6], v[7]);
+                    RR_PACK8(HT, o, v);
                     *reinterpret_cast<uint4*>(dst + cl) = o;
                 }
             }

@@ -23,6 +23,7 @@
 // HBM traffic = x once (per channel slice) + residual once + y once.
 #include "rr_internal.h"
 #include "rr_ldsdma.h"
+#include "rr_epilogue.h"
 
 namespace rr {
 
@@ -153,10 +154,7 @@ __global__ void __launch_bounds__(64 * NW) k_stream1x1(ConvArgs a, int nslices, 
                 int abase = 0;
                 asm volatile("" : "+v"(abase));
                 f32x4_t acc[2][FN];
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int j = 0; j < FN; ++j) acc[h][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+                RR_ZERO(2, acc);
 #pragma unroll
                 for (int kk = 0; kk < NK; ++kk)
 #pragma unroll
@@ -170,39 +168,21 @@ __global__ void __launch_bounds__(64 * NW) k_stream1x1(ConvArgs a, int nslices, 
                     }
                 if (live) {
                     const int cl = 32 * i2 + 8 * kq;  // 8 consecutive channels of this lane
-                    const float4 sc0 = *reinterpret_cast<const float4*>(sS + cl);
-                    const float4 sc1 = *reinterpret_cast<const float4*>(sS + cl + 4);
-                    const float4 sh0 = *reinterpret_cast<const float4*>(sH + cl);
-                    const float4 sh1 = *reinterpret_cast<const float4*>(sH + cl + 4);
-                    const float sc[8] = {sc0.x, sc0.y, sc0.z, sc0.w, sc1.x, sc1.y, sc1.z, sc1.w};
-                    const float sh[8] = {sh0.x, sh0.y, sh0.z, sh0.w, sh1.x, sh1.y, sh1.z, sh1.w};
+                    float sc[8], sh[8];
+                    ld8<float>(sS + cl, sc);
+                    ld8<float>(sH + cl, sh);
 #pragma unroll
                     for (int j = 0; j < FN; ++j) {
                         const long long p = (long long)s * SP + j * 16 + r16;
                         float v[8];
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            v[r] = acc[0][j][r] * sc[r] + sh[r];
-                            v[4 + r] = acc[1][j][r] * sc[4 + r] + sh[4 + r];
-                        }
+                        RR_BN_PAIR(acc[0][j], acc[1][j], sc, sh, v);
                         if constexpr (RES) {
                             const uint4 q = rq[d][j][i2];
-                            const unsigned w4[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                v[2 * r] += H16<H>::lo(w4[r]);
-                                v[2 * r + 1] += H16<H>::hi(w4[r]);
-                            }
+                            RR_ADD_PACKED8(H, q, v);
                         }
-                        if (leaky) {
-#pragma unroll
-                            for (int r = 0; r < 8; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * slope;
-                        }
+                        if (leaky) RR_LEAKY(8, v, slope);
                         uint4 o;
-                        o.x = H16<H>::pack2(v[0], v[1]);
-                        o.y = H16<H>::pack2(v[2], v[3]);
-                        o.z = H16<H>::pack2(v[4], v[5]);
-                        o.w = H16<H>::pack2(v[6], v[7]);
+                        RR_PACK8(H, o, v);
                         if (p < P) st16_once(Y + p * a.ldy + c0 + cl, o);
                     }
                 }
@@ -340,11 +320,7 @@ __global__ void __launch_bounds__(512) k_stream_pair(PairArgs a) {
                     }
                 const int c = 32 * i2 + 8 * kq;
                 float v[8];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v[r] = acc[0][r] * sS3[c + r] + sH3[c + r];
-                    v[4 + r] = acc[1][r] * sS3[c + 4 + r] + sH3[c + 4 + r];
-                }
+                RR_BN_PAIR(acc[0], acc[1], sS3 + c, sH3 + c, v);
                 if constexpr (PROJ) {  // shortcut = proj_bn(proj_conv(x_in)), kept in f32
                     f32x4_t pacc[2] = {(f32x4_t){0.f, 0.f, 0.f, 0.f}, (f32x4_t){0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
@@ -361,28 +337,16 @@ __global__ void __launch_bounds__(512) k_stream_pair(PairArgs a) {
                     }
                 } else {
                     const uint4 q = rq[d][i2];
-                    const unsigned w4[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        v[2 * r] += H16<H>::lo(w4[r]);
-                        v[2 * r + 1] += H16<H>::hi(w4[r]);
-                    }
+                    RR_ADD_PACKED8(H, q, v);
                 }
-                if (leaky3) {
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope3;
-                }
-                yq[i2].x = H16<H>::pack2(v[0], v[1]);
-                yq[i2].y = H16<H>::pack2(v[2], v[3]);
-                yq[i2].z = H16<H>::pack2(v[4], v[5]);
-                yq[i2].w = H16<H>::pack2(v[6], v[7]);
+                if (leaky3) RR_LEAKY(8, v, a.slope3);
+                RR_PACK8(H, yq[i2], v);
                 if (st) st16_once(a.y + p * C3 + c, yq[i2]);
             }
             load(d, strip_of(i + D));  // refill this slot: strip i + D
             // ---- z = act1(W1 y * s1 + h1), y straight from registers
             f32x4_t zacc[NF1];
-#pragma unroll
-            for (int o = 0; o < NF1; ++o) zacc[o] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+            RR_ZERO(1, zacc);
 #pragma unroll
             for (int kk = 0; kk < NK1; ++kk) {
                 int abase = 0;
@@ -397,20 +361,10 @@ __global__ void __launch_bounds__(512) k_stream_pair(PairArgs a) {
             for (int o2 = 0; o2 < NF1 / 2; ++o2) {
                 const int c = 32 * o2 + 8 * kq;
                 float v[8];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v[r] = zacc[2 * o2][r] * sS1[c + r] + sH1[c + r];
-                    v[4 + r] = zacc[2 * o2 + 1][r] * sS1[c + 4 + r] + sH1[c + 4 + r];
-                }
-                if (leaky1) {
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope1;
-                }
+                RR_BN_PAIR(zacc[2 * o2], zacc[2 * o2 + 1], sS1 + c, sH1 + c, v);
+                if (leaky1) RR_LEAKY(8, v, a.slope1);
                 uint4 o;
-                o.x = H16<H>::pack2(v[0], v[1]);
-                o.y = H16<H>::pack2(v[2], v[3]);
-                o.z = H16<H>::pack2(v[4], v[5]);
-                o.w = H16<H>::pack2(v[6], v[7]);
+                RR_PACK8(H, o, v);
                 if (st) st16_once(a.z + p * C1 + c, o);
             }
         }
@@ -531,10 +485,7 @@ __global__ void __launch_bounds__(512, 1) k_pair_mid(PairMidArgs a) {
 #pragma unroll
         for (int i2 = 0; i2 < 2; ++i2) {
             f32x4_t acc[2][4];
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[h][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+            RR_ZERO(2, acc);
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
                 uint4 bx[4];
@@ -550,38 +501,20 @@ __global__ void __launch_bounds__(512, 1) k_pair_mid(PairMidArgs a) {
             }
             const int c = 64 * wave + 32 * i2 + 8 * kq;  // 8 consecutive channels of this lane (PERM32)
             const int chunk = c >> 3;
-            const float4 sc0 = *reinterpret_cast<const float4*>(sS3 + c);
-            const float4 sc1 = *reinterpret_cast<const float4*>(sS3 + c + 4);
-            const float4 sh0 = *reinterpret_cast<const float4*>(sH3 + c);
-            const float4 sh1 = *reinterpret_cast<const float4*>(sH3 + c + 4);
-            const float sc[8] = {sc0.x, sc0.y, sc0.z, sc0.w, sc1.x, sc1.y, sc1.z, sc1.w};
-            const float sh[8] = {sh0.x, sh0.y, sh0.z, sh0.w, sh1.x, sh1.y, sh1.z, sh1.w};
+            float sc[8], sh[8];
+            ld8<float>(sS3 + c, sc);
+            ld8<float>(sH3 + c, sh);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int px = 16 * j + r16;
                 uint4* slot = reinterpret_cast<uint4*>(RY + px * (C3 * 2) + ((chunk ^ (px & 15)) << 4));
-                const uint4 q = *slot;
-                const unsigned w4[4] = {q.x, q.y, q.z, q.w};
                 float v[8];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v[r] = acc[0][j][r] * sc[r] + sh[r];
-                    v[4 + r] = acc[1][j][r] * sc[4 + r] + sh[4 + r];
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v[2 * r] += H16<H>::lo(w4[r]);
-                    v[2 * r + 1] += H16<H>::hi(w4[r]);
-                }
-                if (leaky3) {
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope3;
-                }
+                RR_BN_PAIR(acc[0][j], acc[1][j], sc, sh, v);
+                const uint4 q = *slot;
+                RR_ADD_PACKED8(H, q, v);
+                if (leaky3) RR_LEAKY(8, v, a.slope3);
                 uint4 o;
-                o.x = H16<H>::pack2(v[0], v[1]);
-                o.y = H16<H>::pack2(v[2], v[3]);
-                o.z = H16<H>::pack2(v[4], v[5]);
-                o.w = H16<H>::pack2(v[6], v[7]);
+                RR_PACK8(H, o, v);
                 *slot = o;
                 const long long p = (long long)t * TP + px;
                 if (p < P) st16_once(a.y + p * C3 + c, o);
@@ -592,8 +525,7 @@ __global__ void __launch_bounds__(512, 1) k_pair_mid(PairMidArgs a) {
         if (more) dma_x(t + G);
         // ---- stage 2: z = act1(W1 y * s1 + h1), K = 512 from the LDS y tile
         f32x4_t zacc[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) zacc[j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+        RR_ZERO(1, zacc);
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk) {
             uint4 by[4];
@@ -614,10 +546,7 @@ __global__ void __launch_bounds__(512, 1) k_pair_mid(PairMidArgs a) {
             for (int j = 0; j < 4; ++j) {
                 float v[4] = {zacc[j][0] * sc.x + sh.x, zacc[j][1] * sc.y + sh.y, zacc[j][2] * sc.z + sh.z,
                               zacc[j][3] * sc.w + sh.w};
-                if (leaky1) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope1;
-                }
+                if (leaky1) RR_LEAKY(4, v, a.slope1);
                 uint2 o;
                 o.x = H16<H>::pack2(v[0], v[1]);
                 o.y = H16<H>::pack2(v[2], v[3]);
@@ -721,10 +650,7 @@ __global__ void __launch_bounds__(512, 1) k_pair_mid_ring(PairMidArgs a) {
 #pragma unroll
         for (int i2 = 0; i2 < 2; ++i2) {
             f32x4_t acc[2][2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[h][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+            RR_ZERO(2, acc);
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
                 uint4 bx[2];
@@ -740,38 +666,20 @@ __global__ void __launch_bounds__(512, 1) k_pair_mid_ring(PairMidArgs a) {
             }
             const int c = 64 * wave + 32 * i2 + 8 * kq;  // 8 consecutive channels of this lane (PERM32)
             const int chunk = c >> 3;
-            const float4 sc0 = *reinterpret_cast<const float4*>(sS3 + c);
-            const float4 sc1 = *reinterpret_cast<const float4*>(sS3 + c + 4);
-            const float4 sh0 = *reinterpret_cast<const float4*>(sH3 + c);
-            const float4 sh1 = *reinterpret_cast<const float4*>(sH3 + c + 4);
-            const float sc[8] = {sc0.x, sc0.y, sc0.z, sc0.w, sc1.x, sc1.y, sc1.z, sc1.w};
-            const float sh[8] = {sh0.x, sh0.y, sh0.z, sh0.w, sh1.x, sh1.y, sh1.z, sh1.w};
+            float sc[8], sh[8];
+            ld8<float>(sS3 + c, sc);
+            ld8<float>(sH3 + c, sh);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const int px = 16 * j + r16;
                 uint4* slot = reinterpret_cast<uint4*>(RY + px * (C3 * 2) + ((chunk ^ (px & 15)) << 4));
-                const uint4 q = *slot;
-                const unsigned w4[4] = {q.x, q.y, q.z, q.w};
                 float v[8];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v[r] = acc[0][j][r] * sc[r] + sh[r];
-                    v[4 + r] = acc[1][j][r] * sc[4 + r] + sh[4 + r];
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v[2 * r] += H16<H>::lo(w4[r]);
-                    v[2 * r + 1] += H16<H>::hi(w4[r]);
-                }
-                if (leaky3) {
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope3;
-                }
+                RR_BN_PAIR(acc[0][j], acc[1][j], sc, sh, v);
+                const uint4 q = *slot;
+                RR_ADD_PACKED8(H, q, v);
+                if (leaky3) RR_LEAKY(8, v, a.slope3);
                 uint4 o;
-                o.x = H16<H>::pack2(v[0], v[1]);
-                o.y = H16<H>::pack2(v[2], v[3]);
-                o.z = H16<H>::pack2(v[4], v[5]);
-                o.w = H16<H>::pack2(v[6], v[7]);
+                RR_PACK8(H, o, v);
                 *slot = o;
                 const long long p = (long long)t * TP + px;
                 if (p < P) st16_once(a.y + p * C3 + c, o);
@@ -781,8 +689,7 @@ __global__ void __launch_bounds__(512, 1) k_pair_mid_ring(PairMidArgs a) {
         lds_barrier();
         // ---- stage 2: z = act1(W1 y * s1 + h1), K = 512 from the LDS y tile
         f32x4_t zacc[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) zacc[j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+        RR_ZERO(1, zacc);
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk) {
             uint4 by[2];
@@ -802,10 +709,7 @@ __global__ void __launch_bounds__(512, 1) k_pair_mid_ring(PairMidArgs a) {
             for (int j = 0; j < 2; ++j) {
                 float v[4] = {zacc[j][0] * sc.x + sh.x, zacc[j][1] * sc.y + sh.y, zacc[j][2] * sc.z + sh.z,
                               zacc[j][3] * sc.w + sh.w};
-                if (leaky1) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope1;
-                }
+                if (leaky1) RR_LEAKY(4, v, a.slope1);
                 uint2 o;
                 o.x = H16<H>::pack2(v[0], v[1]);
                 o.y = H16<H>::pack2(v[2], v[3]);
@@ -966,10 +870,7 @@ __global__ void __launch_bounds__(512, 1) k_wres1x1(WresArgs a) {
         const char* X = smem + cur * BUF;
         const char* Rt = X + XB;
         f32x4_t acc[NI][NJ];
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+        RR_ZERO(2, acc);
 #pragma unroll
         for (int kk = 0; kk < NK; ++kk) {
             uint4 bx[NJ];
@@ -986,39 +887,21 @@ __global__ void __launch_bounds__(512, 1) k_wres1x1(WresArgs a) {
 #pragma unroll
         for (int i2 = 0; i2 < CW / 32; ++i2) {
             const int cl = CW * wave + 32 * i2 + 8 * kq;  // 8 consecutive channels of this lane (PERM32)
-            const float4 sc0 = *reinterpret_cast<const float4*>(sS + cl);
-            const float4 sc1 = *reinterpret_cast<const float4*>(sS + cl + 4);
-            const float4 sh0 = *reinterpret_cast<const float4*>(sH + cl);
-            const float4 sh1 = *reinterpret_cast<const float4*>(sH + cl + 4);
-            const float sc[8] = {sc0.x, sc0.y, sc0.z, sc0.w, sc1.x, sc1.y, sc1.z, sc1.w};
-            const float sh[8] = {sh0.x, sh0.y, sh0.z, sh0.w, sh1.x, sh1.y, sh1.z, sh1.w};
+            float sc[8], sh[8];
+            ld8<float>(sS + cl, sc);
+            ld8<float>(sH + cl, sh);
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 const int px = 16 * j + r16;
                 float v[8];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v[r] = acc[2 * i2][j][r] * sc[r] + sh[r];
-                    v[4 + r] = acc[2 * i2 + 1][j][r] * sc[4 + r] + sh[4 + r];
-                }
+                RR_BN_PAIR(acc[2 * i2][j], acc[2 * i2 + 1][j], sc, sh, v);
                 if constexpr (RES) {
                     const uint4 q = *reinterpret_cast<const uint4*>(Rt + px * RRB + (((cl >> 3) ^ (px & 15)) << 4));
-                    const unsigned w4[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        v[2 * r] += H16<H>::lo(w4[r]);
-                        v[2 * r + 1] += H16<H>::hi(w4[r]);
-                    }
+                    RR_ADD_PACKED8(H, q, v);
                 }
-                if (leaky) {
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope;
-                }
+                if (leaky) RR_LEAKY(8, v, a.slope);
                 uint4 o;
-                o.x = H16<H>::pack2(v[0], v[1]);
-                o.y = H16<H>::pack2(v[2], v[3]);
-                o.z = H16<H>::pack2(v[4], v[5]);
-                o.w = H16<H>::pack2(v[6], v[7]);
+                RR_PACK8(H, o, v);
                 const long long p = (long long)t * TP + px;
                 if (p < P) st16_once(a.y + p * a.ldy + c0 + cl, o);
             }

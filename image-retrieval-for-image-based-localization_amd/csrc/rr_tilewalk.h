@@ -58,5 +58,9 @@ inline int persistent_grid8(long long ntiles, int cus) {
     const int grid = (int)(ntiles < cus ? ntiles : cus) & ~7;
     return grid < 8 ? 8 : grid;
 }
+// Host: the grid of a range-walk launch that keeps one block per CU.  A grid below 8 blocks would
+// leave some XCD's tile range without a block (xcd_tile_range needs nwg >= 8), so with fewer than
+// 8 CUs -- or fewer tiles than CUs -- it falls back to one block per tile, the plain bijective remap.
+inline long long range_walk_grid(long long ntiles, long long cus) { return cus < 8 || ntiles < cus ? ntiles : cus; }
 
 }  // namespace rr

@@ -139,6 +139,25 @@ static void tilewalk_case() {
             const int g = rr::persistent_grid8(ntiles, cus);
             EXPECT(g % 8 == 0 && g >= 8 && g <= std::max(8, cus));
         }
+        // the range walk's launch grid: one block per CU or one per tile, the rule the GEMM launch
+        // sites wrote out, and a grid with which the range walk covers every tile exactly once
+        for (int cus : {1, 4, 7, 8, 9, 16, 32, 40}) {
+            const int g = (int)rr::range_walk_grid(ntiles, cus);
+            EXPECT(g == ntiles || g == cus);
+            EXPECT(g == (cus < 8 || ntiles < cus ? ntiles : cus));
+            std::vector<int> xcd(ntiles, -1), times(ntiles, 0);
+            bool inside = true;
+            for (int b = 0; b < g; ++b) {
+                const rr::TileRange r = rr::xcd_tile_range(b, ntiles, g);
+                for (int m = 0; r.li + m * r.nb_x < r.n_x; ++m) {
+                    const int t = r.s_x + r.li + m * r.nb_x;
+                    if (t < 0 || t >= ntiles) { inside = false; continue; }
+                    ++times[t];
+                    xcd[t] = b & 7;
+                }
+            }
+            EXPECT(inside && covers(xcd, times));
+        }
     }
 }
 

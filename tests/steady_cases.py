@@ -59,18 +59,18 @@ def round_robin(items, workers):
 
 # ---------------------------------------------------------------- launch arithmetic
 def wres_cw(K):
-    """launch_stream1x1's launch_wres<K, CW> (rr_stream.hip:1114-1123)"""
+    """launch_stream1x1's launch_wres<K, CW> (rr_stream.hip:997-1006)"""
     return {512: 32, 256: 64, 128: 64}[K]
 
 
 def wres_nbuf(K, res, ring):
-    """k_wres1x1's NBUF (rr_stream.hip:865): 3 with the residual tile or WRES_RING = 0, else 6 where a tile is
+    """k_wres1x1's NBUF (rr_stream.hip:769): 3 with the residual tile or WRES_RING = 0, else 6 where a tile is
     16 KiB (K = 256) and 4 at 32 KiB (K = 512)"""
     return 3 if res or not ring else (6 if 32 * K * 2 <= 16384 else 4)
 
 
 def wres_plan(P, C, BC, cap):
-    """launch_wres (rr_stream.hip:1065-1083): C / BC channel slices, cap / slices blocks per slice, 32-pixel tiles"""
+    """launch_wres (rr_stream.hip:948-966): C / BC channel slices, cap / slices blocks per slice, 32-pixel tiles"""
     nslices = C // BC
     per = max(cap // nslices, 1)
     ntiles = ceil_div(P, 32)
@@ -80,7 +80,7 @@ def wres_plan(P, C, BC, cap):
 
 
 def stream_plan(P, TC, K, FN, D, NW, C, cap):
-    """launch_s_t (rr_stream.hip:1033-1043): strips of 16 FN pixels over per_slice x NW waves per channel slice"""
+    """launch_s_t (rr_stream.hip:916-926): strips of 16 FN pixels over per_slice x NW waves per channel slice"""
     lds = TC * K * 2 + TC * 8
     per_cu = (4 if NW <= 4 else 2) if (160 * 1024 // lds) >= 2 and NW <= 8 else 1
     nslices = C // TC
@@ -91,7 +91,7 @@ def stream_plan(P, TC, K, FN, D, NW, C, cap):
 
 
 def stream_variant(K, C):
-    """(TC, K, FN, D, NW) of launch_stream1x1's table (rr_stream.hip:1129-1149)"""
+    """(TC, K, FN, D, NW) of launch_stream1x1's table (rr_stream.hip:1012-1032)"""
     table = {(64, 64): (64, 64, 2, 4, 8), (64, 256): (256, 64, 1, 2, 8), (256, 64): (64, 256, 1, 4, 8),
              (256, 128): (128, 256, 1, 3, 8), (128, 512): (256, 128, 1, 3, 8), (512, 128): (128, 512, 1, 2, 8),
              (256, 1024): (256, 256, 1, 2, 8), (256, 512): (256, 256, 1, 2, 8), (512, 2048): (128, 512, 1, 2, 8),
@@ -100,21 +100,21 @@ def stream_variant(K, C):
 
 
 def pair_plan(P, cap):
-    """rr_conv1x1_pair, the 64 / 256 boundary (rr_stream.hip:1213-1215): 16-pixel strips, 8 waves per block"""
+    """rr_conv1x1_pair, the 64 / 256 boundary (rr_stream.hip:1096-1098): 16-pixel strips, 8 waves per block"""
     nstrips = ceil_div(P, 16)
     grid = min(ceil_div(nstrips, 8), cap)
     return Plan(grid, grid, 0, 0, round_robin(nstrips, grid * 8))
 
 
 def mid_plan(P, cap, TP):
-    """rr_conv1x1_pair, the 128 / 512 boundary (rr_stream.hip:1195-1196): TP = 32 (k_pair_mid_ring) or 64 (k_pair_mid)"""
+    """rr_conv1x1_pair, the 128 / 512 boundary (rr_stream.hip:1078-1079): TP = 32 (k_pair_mid_ring) or 64 (k_pair_mid)"""
     ntiles = ceil_div(P, TP)
     grid = min(ntiles, cap)
     return Plan(grid, grid, 0, 0, round_robin(ntiles, grid))
 
 
 def c3pair_plan(n, h, w, cap):
-    """rr_conv3x3_pair (rr_c3pair.hip:584-588) and k_c3pair's two tile walks (rr_c3pair.hip:147-155, rr_tilewalk.h) ->
+    """rr_conv3x3_pair (rr_c3pair.hip:535-539) and k_c3pair's two tile walks (rr_c3pair.hip:148-156, rr_tilewalk.h) ->
     (static Plan, dynamic Plan).  4 x 32 tiles, a grid of a multiple of 8 blocks (at least 8).  Static: block b takes
     tiles i G + (b & 7) (G / 8) + (b >> 3); counts per block.  Dynamic: XCD x owns a contiguous range of
     ntiles / 8 (+ 1) tiles that its G / 8 blocks share through a counter; counts per XCD (per block where G = 8)."""
@@ -126,14 +126,14 @@ def c3pair_plan(n, h, w, cap):
 
 
 def c3_plan(n, h, w, c_out, TC, TH, TW, cap):
-    """launch_c3 (rr_conv3.hip:563-566) and k_conv3x3's walk (rr_conv3.hip:83-87): block b takes tiles b, b + G, ..."""
+    """launch_c3 (rr_conv3.hip:528-531) and k_conv3x3's walk (rr_conv3.hip:84-88): block b takes tiles b, b + G, ..."""
     ntiles = n * (h // TH) * (w // TW) * (c_out // TC)
     grid = min(ntiles, cap)
     return Plan(grid, grid, c_out // TC, 0, round_robin(ntiles, grid))
 
 
 def c3w64_plan(n, h, w, cap):
-    """the k_c3w64 site (rr_conv3.hip:602-605) and its round walk (rr_conv3.hip:449, rr_tilewalk.h): 8 x 32 tiles"""
+    """the k_c3w64 site (rr_conv3.hip:567-570) and its round walk (rr_conv3.hip:427, rr_tilewalk.h): 8 x 32 tiles"""
     ntiles = n * (h // 8) * (w // 32)
     grid = max(min(ntiles, cap) & ~7, 8)
     counts = sorted({c for c in (len(range((b & 7) * (grid >> 3) + (b >> 3), ntiles, grid)) for b in range(grid)) if c})
@@ -141,7 +141,7 @@ def c3w64_plan(n, h, w, cap):
 
 
 def c3_variant(c_in, c_out, h, mode, cap, n=0, w=0):
-    """launch_conv3x3's choice under CONV3S = 0 (rr_conv3.hip:602-641) -> ("k_c3w64", None) or
+    """launch_conv3x3's choice under CONV3S = 0 (rr_conv3.hip:567-606) -> ("k_c3w64", None) or
     ("k_conv3x3", (TC, TH, TW, WC, WP, NSA))"""
     if c_in == 64 and c_out == 64 and h % 8 == 0:
         if mode in (9, 1):

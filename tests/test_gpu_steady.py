@@ -203,7 +203,7 @@ def test_conv3x3_past_two_tiles(cuda, dt, row):
             else:
                 want = ("k_conv3x3", "%d,%d,%d,%d,%d,%d,pipe%d" % (*v, pipe), 64 * v[3] * v[4], SC.c3_plan(n, h, w, cout, *v[:3], cap))
             variants.append(("mode %d pipe %d" % (mode, pipe), cap, tune, want))
-    # uncapped, modes 2 and 7 choose their tile height by the CU count (rr_conv3.hip:622): the name only there
+    # uncapped, modes 2 and 7 choose their tile height by the CU count (rr_conv3.hip:587): the name only there
     conv_row(cuda, dt, "direct 3x3", cin, cout, 3, (n, h, w), 1, False, leaky, variants, uncapped_variant=False)
 
 

@@ -101,7 +101,7 @@ def test_stream_rows_rotate_past_the_depth():
             assert (plan.nslices, plan.xmap, plan.counts) == STREAM_EXPECT[(k, c, res, SC.pixels(shape, stride), cap)], (row, cap, plan)
         assert wraps(union(stream_plans(row)), d), row
         assert SC.pixels(shape, stride) >= 4096 and SC.pixels(shape, stride) % (16 * fn)
-        # k_wres1x1 must not take the shape (rr_stream.hip:1114-1123): WRES = 0, or 1 for a plain form (only WRES = 2 gives it those)
+        # k_wres1x1 must not take the shape (rr_stream.hip:997-1006): WRES = 0, or 1 for a plain form (only WRES = 2 gives it those)
         assert wres == 0 or (wres == 1 and not res), row
     plans = [p for row in SC.STREAM_ROWS for p in stream_plans(row)]
     assert {p.xmap for p in plans} == {0, 1} and any(len(p.counts) > 1 for p in plans)
