@@ -124,6 +124,10 @@ _SIGS = {
                          _vp], _i),
     "rr_triangulate_points": ([_vp, _vp, _vp, _vp, _vp, _ll, _i, _vp, _vp], _i),
     "rr_essential_decompose": ([_vp, _i, _vp, _vp, _vp, _vp], _i),
+    "rr_localize_workspace_bytes": ([_ll, _i, _i], _sz),
+    "rr_localize_pairs": ([_vp, _vp, _ll, _vp, _vp, _vp, _ll, _vp, _i, _i, _vp, _d, _i, _i, ctypes.c_ulonglong, _vp, _vp, _vp,
+                           _vp, _vp, _sz, _vp], _i),
+    "rr_p3p": ([_vp, _vp, _i, _vp, _vp, _vp, _vp], _i),
     "rr_patchnet_packed_bytes": ([], _sz),
     "rr_patchnet_pack": ([ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _sz, _vp], _i),
     "rr_patchnet_workspace_bytes": ([_ll], _sz),

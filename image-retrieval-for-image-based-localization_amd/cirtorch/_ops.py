@@ -900,6 +900,57 @@ def essential_decompose(Em):
     return R1, R2, t
 
 
+# ---------------------------------------------------------------- localization (absolute pose)
+def localize_pairs(kp1, off1, pts3d, valid, off2, match, K, th=3.0, iters=1024, refine=2, seed=0, max_n1=None, covered=False):
+    """rr_localize_pairs: kp1 [rows1, 2] float32 pixel keypoints, pts3d float64 [rows2, 3], valid uint8 / bool
+    [rows2] or None, device int64 offsets [P + 1], match int64 [rows1], K float64 [P, 3, 3] ->
+    (inliers int32 [P], R float64 [P, 3, 3], t float64 [P, 3], mask uint8 [rows1]).  covered=True: the
+    pairs cover every side-1 row (the mask is not pre-filled with 0).  No synchronisation."""
+    E.require_gpu(kp1, off1, pts3d, valid, off2, match, K)
+    if kp1.dim() != 2 or kp1.shape[1] != 2 or kp1.dtype != torch.float32 or not kp1.is_contiguous():
+        raise RuntimeError("localize: keypoints must be contiguous float32 [rows1, 2], got %s %s" % (kp1.dtype, tuple(kp1.shape)))
+    if pts3d.dim() != 2 or pts3d.shape[1] != 3 or pts3d.dtype != torch.float64 or not pts3d.is_contiguous():
+        raise RuntimeError("localize: points3d must be contiguous float64 [rows2, 3], got %s %s" % (pts3d.dtype, tuple(pts3d.shape)))
+    if off1.dtype != torch.int64 or off2.dtype != torch.int64 or off1.numel() != off2.numel() or off1.numel() < 1:
+        raise RuntimeError("localize: offsets must be int64 [P + 1] for both sides")
+    rows1, rows2, npairs = kp1.shape[0], pts3d.shape[0], off1.numel() - 1
+    if match.dtype != torch.int64 or match.dim() != 1 or match.shape[0] != rows1 or not match.is_contiguous():
+        raise RuntimeError("localize: match must be contiguous int64 [rows1]")
+    if valid is not None and (valid.dtype not in (torch.uint8, torch.bool) or tuple(valid.shape) != (rows2,)
+                              or not valid.is_contiguous()):
+        raise RuntimeError("localize: valid must be contiguous uint8 or bool [rows2]")
+    if K.dtype != torch.float64 or tuple(K.shape) != (npairs, 3, 3) or not K.is_contiguous():
+        raise RuntimeError("localize: K must be contiguous float64 [P, 3, 3], got %s %s" % (K.dtype, tuple(K.shape)))
+    max_n1 = rows1 if max_n1 is None else min(int(max_n1), rows1)
+    dev = kp1.device
+    inliers = torch.empty(npairs, dtype=torch.int32, device=dev)   # written for every pair
+    R = torch.empty((npairs, 3, 3), dtype=torch.float64, device=dev)
+    t = torch.empty((npairs, 3), dtype=torch.float64, device=dev)
+    mask = (torch.empty if covered and npairs else torch.zeros)(rows1, dtype=torch.uint8, device=dev)
+    ws = _workspace(E.lib().rr_localize_workspace_bytes(rows1, npairs, int(iters)), dev)
+    E.check(E.lib().rr_localize_pairs(E.ptr(kp1), E.ptr(off1), rows1, E.ptr(pts3d), E.ptr(valid), E.ptr(off2), rows2,
+                                      E.ptr(match), npairs, max_n1, E.ptr(K), float(th), int(iters), int(refine),
+                                      int(seed) & 0xFFFFFFFFFFFFFFFF, E.ptr(inliers), E.ptr(R), E.ptr(t), E.ptr(mask),
+                                      E.ptr(ws), ws.numel(), _st()), "rr_localize_pairs")
+    return inliers, R, t, mask
+
+
+def p3p(x, X):
+    """rr_p3p: x float64 [n, 3, 2] normalised image points, X float64 [n, 3, 3] -> (R float64 [n, 4, 3, 3],
+    t float64 [n, 4, 3] in ascending root order, zeros past nsol; nsol int32 [n]).  No synchronisation."""
+    E.require_gpu(x, X)
+    if x.dim() != 3 or tuple(x.shape[1:]) != (3, 2) or X.dim() != 3 or tuple(X.shape[1:]) != (3, 3) or x.shape[0] != X.shape[0]:
+        raise RuntimeError("p3p: points must be [n, 3, 2] and [n, 3, 3], got %s and %s" % (tuple(x.shape), tuple(X.shape)))
+    if x.dtype != torch.float64 or X.dtype != torch.float64 or not x.is_contiguous() or not X.is_contiguous():
+        raise RuntimeError("p3p: points must be contiguous float64")
+    n = x.shape[0]
+    R = torch.empty((n, 4, 3, 3), dtype=torch.float64, device=x.device)
+    t = torch.empty((n, 4, 3), dtype=torch.float64, device=x.device)
+    nsol = torch.empty(n, dtype=torch.int32, device=x.device)
+    E.check(E.lib().rr_p3p(E.ptr(x), E.ptr(X), n, E.ptr(R), E.ptr(t), E.ptr(nsol), _st()), "rr_p3p")
+    return R, t, nsol
+
+
 # ---------------------------------------------------------------- keypoint detection
 RESPONSES = {"harris": E.RR_RESP_HARRIS, "gftt": E.RR_RESP_GFTT, "hessian": E.RR_RESP_HESSIAN}
 NMS_SIZES = (3, 5, 7, 9)

@@ -810,6 +810,82 @@ def recover_pose(kpts1, kpts2, match, F, K1, K2, mask=None, offsets1=None, offse
     return R, t.unsqueeze(-1), pts.view(tuple(match.shape) + (3,)), fmask.view(torch.bool).view(match.shape), front
 
 
+def localize_pairs(kpts, points3d, match, K, th=3.0, iters=1024, refine=2, seed=0, valid=None, offsets1=None, offsets2=None,
+                   max_n1=None):
+    """The pose of a query camera against the 3-D points of each database image it was matched to, in
+    one call (rr_localize_pairs): per pair a RANSAC pose from three-point samples (P3P), refitted
+    `refine` times by Gauss-Newton on the reprojection error of its inliers.  The last step of a
+    localization pipeline; every input comes from the steps before it:
+
+        inl, F, m = verify_pairs(a_kpts, b_kpts, match_ab, th=1.5, model="fundamental")
+        Rab, tab, X, front_mask, front = recover_pose(a_kpts, b_kpts, match_ab, F, Ka, Kb, mask=m)
+        match_qa, _ = match_pairs(q_desc, a_desc, mode="smnn")
+        inl, R, t, mask = localize_pairs(q_kpts, X, match_qa, Kq, th=3.0, valid=front_mask)   # query pose in view a's frame, in units of |tab|
+
+    ``points3d`` and ``front_mask`` of ``recover_pose`` are indexed by view a's keypoint rows, and
+    ``match_pairs(query, view a)`` returns indices into exactly those rows.  float64 on float32 pixel
+    keypoints (x, y); `iters` hypotheses per pair drawn by the counter hash of ``verify_pairs``, so a
+    result is bit-identical run to run and does not depend on the batch.
+
+    dense   kpts [P, N1, 2], points3d [P, N2, 3], match int64 [P, N1], valid bool [P, N2] or None
+            (or [N1, 2], [N2, 3], [N1], [N2] for one pair), K [3, 3] (one camera for every pair) or [P, 3, 3]
+            -> inliers int32 [P], R float64 [P, 3, 3], t float64 [P, 3, 1], mask bool [P, N1]
+    ragged  kpts [rows1, 2], points3d [rows2, 3], match [rows1], valid [rows2] with the device int64
+            offsets1 / offsets2 [P + 1] of ``match_pairs`` -> mask [rows1] (max_n1: optional host bound
+            of a pair's side-1 length)
+
+    ``[x, y, 1]^T ~ K (R X + t)``.  points3d is float64 (what ``recover_pose`` writes) or float32,
+    converted once.  A row counts where its match is kept, `valid` (when given) marks its 3-D point and
+    the point is finite; inliers counts the rows whose point lies in front of the camera and
+    reprojects within `th` pixels, mask marks them.  Fewer than 3 such rows, a K that cannot be
+    inverted, or no sample with an inlier give 0, an all-zero R and t and an empty mask.
+    ``rerank_by_inliers`` takes these counts as it takes ``verify_pairs``'.  No device->host
+    synchronisation: graph-capturable for fixed shapes."""
+    if (offsets1 is None) != (offsets2 is None):
+        raise ValueError("localize_pairs: give both offsets1 and offsets2 (ragged) or neither (dense)")
+    if kpts.shape[-1] != 2 or points3d.shape[-1] != 3:
+        raise ValueError("localize_pairs: keypoints are (x, y) rows and points3d (X, Y, Z) rows, got %s and %s"
+                         % (tuple(kpts.shape), tuple(points3d.shape)))
+    if int(iters) < 1 or int(refine) < 0 or not (float(th) > 0.0 and float(th) < float("inf")):
+        raise ValueError("localize_pairs: iters >= 1, refine >= 0 and a positive finite th, got %r, %r, %r" % (iters, refine, th))
+    if match.dtype != torch.int64:
+        raise ValueError("localize_pairs: match must be int64 (the output of match_pairs), got %s" % match.dtype)
+    if points3d.dtype not in (torch.float32, torch.float64):
+        raise ValueError("localize_pairs: points3d must be float64 or float32, got %s" % points3d.dtype)
+    if valid is not None and (tuple(valid.shape) != tuple(points3d.shape[:-1]) or valid.dtype not in (torch.bool, torch.uint8)):
+        raise ValueError("localize_pairs: valid must be bool or uint8 of shape %s, got %s %s"
+                         % (tuple(points3d.shape[:-1]), valid.dtype, tuple(valid.shape)))
+    if offsets1 is not None:
+        if kpts.dim() != 2 or points3d.dim() != 2 or match.dim() != 1 or match.shape[0] != kpts.shape[0]:
+            raise ValueError("localize_pairs: the ragged form takes [rows1, 2] keypoints, [rows2, 3] points and match [rows1]")
+        p = offsets1.numel() - 1
+        if offsets2.numel() != p + 1 or p < 0:
+            raise ValueError("localize_pairs: offsets1 and offsets2 must both be [P + 1]")
+        Km = _pose_mats(K, p, "K", "localize_pairs")
+        _ops.E.require_gpu(kpts, points3d, match, valid, offsets1, offsets2, K)
+        inl, R, t, mask = _ops.localize_pairs(kpts.float().contiguous(), offsets1.contiguous(), points3d.double().contiguous(),
+                                              None if valid is None else valid.contiguous(), offsets2.contiguous(),
+                                              match.contiguous(), Km, th, iters, refine, seed, max_n1)
+        return inl, R, t.unsqueeze(-1), mask.view(torch.bool)
+    if kpts.dim() != points3d.dim() or kpts.dim() not in (2, 3) or (kpts.dim() == 3 and kpts.shape[0] != points3d.shape[0]) \
+            or tuple(match.shape) != tuple(kpts.shape[:-1]):
+        raise ValueError("localize_pairs: dense inputs are [P, N1, 2] keypoints and [P, N2, 3] points (or [N1, 2] and [N2, 3]) "
+                         "with match [P, N1] or [N1], got %s, %s and %s"
+                         % (tuple(kpts.shape), tuple(points3d.shape), tuple(match.shape)))
+    p = kpts.shape[0] if kpts.dim() == 3 else 1
+    n1, n2 = kpts.shape[-2], points3d.shape[-2]
+    if max_n1 is not None and int(max_n1) < n1:
+        raise ValueError("localize_pairs: max_n1 = %d below the pairs' length %d" % (int(max_n1), n1))
+    Km = _pose_mats(K, p, "K", "localize_pairs")
+    _ops.E.require_gpu(kpts, points3d, match, valid, K)
+    steps = torch.arange(p + 1, dtype=torch.int64, device=kpts.device)
+    inl, R, t, mask = _ops.localize_pairs(kpts.float().reshape(p * n1, 2).contiguous(), steps * n1,
+                                          points3d.double().reshape(p * n2, 3).contiguous(),
+                                          None if valid is None else valid.reshape(p * n2).contiguous(), steps * n2,
+                                          match.reshape(p * n1).contiguous(), Km, th, iters, refine, seed, n1, covered=True)
+    return inl, R, t.unsqueeze(-1), mask.view(torch.bool).view(match.shape)
+
+
 def rerank_by_inliers(idx, inliers):
     """Re-order a [k, Q] shortlist (``knn``'s ranks: column q lists query q's database rows, best
     first) by the verified inlier counts [k, Q] of its entries: (inliers desc, original rank

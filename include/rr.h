@@ -687,6 +687,91 @@ int rr_triangulate_points(const double* pts1, const double* pts2, const double* 
  * anything is enqueued; n == 0 returns RR_OK. */
 int rr_essential_decompose(const double* E, int n, double* R1, double* R2, double* t, void* stream);
 
+/* Localization: the absolute pose of a camera against known 3-D points (rr_pnp.hip, rr_p3p.h) -- a
+ * RANSAC pose per pair from three-point samples (P3P), refitted by Gauss-Newton on the reprojection
+ * error of its inliers.  The step after rr_recover_pose: side 1 is the query image's keypoints, side 2
+ * the 3-D points of a database image (points3d and front_mask of rr_recover_pose are indexed by that
+ * image's keypoint rows, and rr_match_pairs(query, that image) returns indices into those rows).  The
+ * upstream project has no absolute pose (it calls OpenCV on the host for its geometry): every rule is
+ * this entry's own.  kp1, off1, rows1, off2, rows2, match, npairs, max_n1, th, iters, refine and seed
+ * are those of rr_verify_pairs_essential.
+ *   pts3d [rows2][3]   float64 3-D points in any world frame, 8-byte aligned
+ *   valid [rows2]      uint8 or NULL (every point): front_mask of rr_recover_pose
+ *   K [npairs][3][3]   float64 row-major intrinsics of the query camera, DEVICE, 16-byte aligned
+ *   inliers [npairs] int32;  R [npairs][3][3], t [npairs][3] float64;  mask [rows1] uint8
+ * The pose satisfies [x, y, 1]^T ~ K (R X + t).  All arithmetic is float64, every sum has a fixed
+ * order, and a result depends on the pair's own data only.  Per pair p:
+ *  a. records: row i < min(n1, max_n1) is kept where 0 <= match[i] < n2, valid is NULL or
+ *     valid[match[i]] != 0, and the three coordinates of X = pts3d[match[i]] are finite; as
+ *     (x, y, X, Y, Z) in float64 in ascending i; M of them.  K^-1 by the adjugate divided by the
+ *     determinant; step a of rr_verify_pairs_essential's failure rule for K fails the pair (step e).
+ *  b. hypothesis t in [0, iters): three distinct record indices by the hash and the partial
+ *     Fisher-Yates draw of rr_verify_pairs with j = 0, 1, 2 (the first three of that entry's four).
+ *     P3P by Grunert's elimination on the records 1, 2, 3 of the sample:
+ *       j_k = h_k / |h_k|, h_k = K^-1 [x_k, y_k, 1]^T;
+ *       a^2 = |X2 - X3|^2, b^2 = |X1 - X3|^2, c^2 = |X1 - X2|^2;  ca = j2 . j3, cb = j1 . j3, cg = j1 . j2;
+ *       q = (a^2 - c^2) / b^2, p = (a^2 + c^2) / b^2;
+ *     with s_k the distance of point k along j_k, v = s3 / s1 is a root of A4 v^4 + .. + A0:
+ *       A4 = (q - 1)^2 - 4 (c^2 / b^2) ca^2
+ *       A3 = 4 [q (1 - q) cb - (1 - p) ca cg + 2 (c^2 / b^2) ca^2 cb]
+ *       A2 = 2 [q^2 - 1 + 2 q^2 cb^2 + 2 ((b^2 - c^2) / b^2) ca^2 - 4 p ca cb cg + 2 ((b^2 - a^2) / b^2) cg^2]
+ *       A1 = 4 [-q (1 + q) cb + 2 (a^2 / b^2) cg^2 cb - (1 - p) ca cg]
+ *       A0 = (1 + q)^2 - 4 (a^2 / b^2) cg^2
+ *     Real roots by the root rule of step b.3 of rr_verify_pairs_essential at degree 4 (A4 == 0 or a
+ *     coefficient that is not finite gives none; the bound 1 + max |A_i / A4|; for d = 1 .. 4 the roots
+ *     of derivative number 4 - d from those of derivative number 5 - d; 48 bisections, 3 guarded Newton
+ *     steps): every simple real root, in ascending order; double roots are not found.  Per root v:
+ *       u = [(q - 1) v^2 - 2 q cb v + 1 + q] / (2 (cg - v ca));
+ *       s1 = b / sqrt(1 + v^2 - 2 v cb), s2 = u s1, s3 = v s1;
+ *     the root is kept where v > 0, u > 0, s1 > 0 and s1, s2, s3 are finite.  Solution number r is the
+ *     r-th kept root in ascending v; at most 4.  Its pose, from Y_k = s_k j_k: with
+ *       e1 = (X2 - X1) / |X2 - X1|,  e3 = e1 x (X3 - X1) normalised,  e2 = e3 x e1
+ *     and f1, f2, f3 the same construction on Y:  R = [f1 f2 f3] [e1 e2 e3]^T,  t = Y1 - R X1.
+ *     A sample gives no solution where b^2 is not > 0, |e1 x (X3 - X1)| is not > 0, or R or t of a kept
+ *     root has an entry that is not finite.
+ *  c. score of a solution: with P = K [R | t] (3 x 4) and (pc0, pc1, pc2) = P [X, Y, Z, 1]^T, the
+ *     number of records with pc2 > 0 and (pc0 - x pc2)^2 + (pc1 - y pc2)^2 <= th^2 pc2^2 -- the
+ *     reprojection error at most th pixels without the division; a point behind the camera never
+ *     counts.  The winner is (score desc, t asc, solution asc).
+ *  d. refit, `refine` times: S = the inliers of (R, t), fixed for the round; while |S| >= 4,
+ *     RR_PNP_GN_STEPS Gauss-Newton steps on the sum over S of |r_i|^2, r_i = (pc0 / pc2 - x,
+ *     pc1 / pc2 - y) with pc = K Xc, Xc = R X + t of the current iterate; a record of S with pc2 not
+ *     > 0 contributes nothing to that step.  Left perturbation Xc' = exp([w]x) Xc + tau: the 2 x 6
+ *     Jacobian of r_i in (w, tau) is D K [-[Xc]x | I], D = [[1, 0, -pc0 / pc2], [0, 1, -pc1 / pc2]] / pc2.
+ *     The 21 entries of the upper triangle of H = sum J^T J and the 6 of g = sum J^T r are summed
+ *     per thread over i = tid, tid + 256, .. and over the block in the fixed order of
+ *     rr_homography_dlt's sums; H d = -g by Cholesky without pivoting, and a pivot that is not > 0 or
+ *     not finite stops the refit.  R <- exp([w]x) R, t <- exp([w]x) t + tau with exp([w]x) =
+ *     I + A [w]x + B [w]x^2, A = sin(a) / a, B = (1 - cos(a)) / a^2, a = |w|, and the series
+ *     A = 1 - a^2 / 6, B = 1/2 - a^2 / 24 where a^2 < RR_PNP_SMALL_ANGLE2.  The new pose replaces
+ *     the old one when it is finite and its score does not drop; otherwise (and when |S| < 4) the
+ *     refit stops.
+ *  e. inliers[p] = the score of (R, t); mask [rows1] uint8 = 1 on the side-1 rows that are kept
+ *     (step a) and inliers (step c); every row of the pair (below max_n1) is written; R and t are
+ *     the final pose.  M < 3, a failed K or no solution with a score above 0: inliers 0, R and t all
+ *     zeros, mask 0.
+ * Not here: EPnP / DLT on more than three points, local optimisation inside the loop, early
+ * termination, lens distortion.  workspace: rr_localize_workspace_bytes(rows1, npairs, iters).  Nothing
+ * waits for the host (graph-capturable).  Bad arguments (null pointers, negative sizes, iters < 1 or
+ * above 2^24, refine < 0, th <= 0 or not finite, max_n1 > rows1, a null or misaligned K, a short
+ * workspace) return an error before anything is enqueued; npairs == 0 returns RR_OK and launches
+ * nothing. */
+#define RR_PNP_GN_STEPS 3
+#define RR_PNP_SMALL_ANGLE2 1e-8
+size_t rr_localize_workspace_bytes(long long rows1, int npairs, int iters);
+int rr_localize_pairs(const float* kp1, const long long* off1, long long rows1, const double* pts3d,
+                      const unsigned char* valid, const long long* off2, long long rows2, const long long* match,
+                      int npairs, int max_n1, const double* K, double th, int iters, int refine, unsigned long long seed,
+                      int* inliers, double* R, double* t, unsigned char* mask, void* workspace, size_t workspace_bytes,
+                      void* stream);
+/* The three-point solver of step b above alone, one thread per sample.
+ *   x [n][3][2]     float64 normalised image points (h = [x, y, 1], K = I), 8-byte aligned
+ *   X [n][3][3]     float64 3-D points
+ *   R [n][4][3][3], t [n][4][3]  float64: the solutions in ascending v; all zeros past nsol[i]
+ *   nsol [n]        int32
+ * n < 0 and null pointers are refused before anything is enqueued; n == 0 returns RR_OK. */
+int rr_p3p(const double* x, const double* X, int n, double* R, double* t, int* nsol, void* stream);
+
 /* Keypoint detection (rr_detect.hip): corner / blob responses, 2-D non-maxima suppression and the
  * best N local maxima per image.  Replaces harris_response, gftt_response and hessian_response of
  * cirtorch/features/responses.py:8-103 (spatial_gradient of cirtorch/filters/sobel.py:12-45,
